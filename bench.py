@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- composed frames/s of the MI355X scroll composer.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload p720dyn|p720|p4kdyn|p720hint|p720splice|ingest720|ipcm720]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                    [--workload p720dyn|p720|p4kdyn|p720hint|p720splice|ingest720|ipcm720]
 
 One process per GPU (torch.distributed.run for N > 1; RANK / LOCAL_RANK /
 WORLD_SIZE from the env).  Streams are independent, so each rank owns a static
@@ -39,11 +40,16 @@ A step = one scroll_batch_compose over every stream of the rank:
   Offsets = SURVEY 8(d) synthetic scroll (speed 1+(s%8), phase 97 s mod 1440)
   in HBM; output arenas are rewound on device at every step (the bytes of a
   step are the product).
-Prints ONE JSON line (rank 0) with the dominant kernel's roofline (k_dyn_row
-for the dynamic rect, k_hint_stage, k_emit; HIP events on its launch stream),
-the CPU oracle on host cores (rank 0, N = 1) and, after the timed region, the
-check of the last step's bytes against the oracle ("verified"; a mismatch
-exits with status 3).  --gpus N without a launcher starts N ranks itself.
+Prints ONE JSON line (rank 0) with the headline figure, ms_per_step and the
+dominant kernel's roofline (k_dyn_row for the dynamic rect, k_hint_stage,
+k_emit; HIP events on its launch stream inside the timed steps).  A plain run
+does no more than that.  --full adds, after the timed region, the CPU oracle
+on host cores (rank 0, N = 1), the check of the last step's bytes against the
+oracle ("verified"; a mismatch exits with status 3) and the host-delivery /
+single-frame latency legs; --no-cpu / --no-verify / --no-host drop one of
+them.  --dump-outputs DIR writes the last timed step's outputs (every
+product's size and CRC-32, a fixed sample of the bytes) as DIR/<name>.npy.
+--gpus N without a launcher starts N ranks itself.
 """
 import argparse
 import ctypes
@@ -158,6 +164,56 @@ def ipcm_ref_file(w, h, which):
     return nal(0x67, _bits_to_bytes(sps)) + nal(0x68, _bits_to_bytes(pps)) + nal(0x65, bytes(body))
 
 
+DUMP_SAMPLE_BYTES = 12 << 20    # sampled output bytes per dump (48 MB as float32)
+
+
+def dump_outputs(dirname, rank, world, sizes, read):
+    """--dump-outputs: what the last timed step produced, as .npy files, so
+    that two builds can be compared output for output.  A product is one
+    stream's bytes of the step (or one file); sizes[k] is its size and
+    read(k, n) returns its first n bytes.
+      sizes.npy         float64 [K]  bytes of every product
+      crc32.npy         float64 [K]  zlib.crc32 of every product's bytes
+      sample_index.npy  float64 [M]  the products kept whole: a fixed walk
+                                     (seed 0 permutation) while they fit
+                                     DUMP_SAMPLE_BYTES (the first one cut to
+                                     fit if it alone is larger)
+      sample_bytes.npy  float32      those products' bytes, concatenated
+    With more than one rank every rank writes its shard as <name>_rank<r>.npy."""
+    import zlib
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    K = len(sizes)
+    picked, room = [], DUMP_SAMPLE_BYTES
+    for k in (int(k) for k in np.random.default_rng(0).permutation(K)):
+        n = sizes[k] if picked else min(sizes[k], room)
+        if n > room:
+            break
+        picked.append(k)
+        room -= n
+    crc = np.zeros(K, np.float64)
+    kept = {}
+    for k in range(K):
+        data = read(k, sizes[k])
+        crc[k] = zlib.crc32(data)
+        if k in picked:
+            kept[k] = np.frombuffer(data[:DUMP_SAMPLE_BYTES], np.uint8)
+    sample = np.concatenate([kept[k] for k in picked]).astype(np.float32) if picked \
+        else np.zeros(0, np.float32)
+    tail = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(dirname, f"sizes{tail}.npy"), np.asarray(sizes, np.float64))
+    np.save(os.path.join(dirname, f"crc32{tail}.npy"), crc)
+    np.save(os.path.join(dirname, f"sample_index{tail}.npy"), np.asarray(picked, np.float64))
+    np.save(os.path.join(dirname, f"sample_bytes{tail}.npy"), sample)
+
+
+def dump_batch_outputs(args, rank, world, b, first, count):
+    """dump_outputs over streams first .. first + count - 1 of batch b"""
+    if args.dump_outputs:
+        sizes = [b.output_size(first + k) for k in range(count)]
+        dump_outputs(args.dump_outputs, rank, world, sizes, lambda k, n: b.output(first + k, 0, n))
+
+
 def oracle_lib():
     """CHECKER / CPU baseline only: oracle/_build/liboracle.so (built on demand)"""
     repo_oracle = os.path.join(HERE, "oracle")
@@ -266,6 +322,7 @@ def run_ingest(args, wl, rank, world, local, dist):
     out_bytes = b.output_size(S * nsteps - 1)
     b.enable_timing(False)
     el = max_over_ranks(t1 - t0, dist)
+    dump_batch_outputs(args, rank, world, b, S * (nsteps - 1), S)
     verified, vdetail = (None, None) if args.no_verify else verify_ingest_step(b, (fa, fb), S * (nsteps - 1), S)
     if rank == 0:
         k_ms = kms / max(kn, 1)
@@ -357,6 +414,9 @@ def run_ipcm(args, wl, rank, world, local, dist):
     kms, kn = b.ipcm_stats()
     b.enable_timing(False)
     el = max_over_ranks(t1 - t0, dist)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, sizes,
+                     lambda k, n: out[k * ostride:k * ostride + n].cpu().numpy().tobytes())
     verified, vdetail = (None, None) if args.no_verify else verify_ipcm_step(pics, out, sizes, ostride, W, H)
     if rank == 0:
         k_ms = kms / max(kn, 1)
@@ -705,6 +765,7 @@ def run_splice(args, wl, rank, world, local, dist):
     b.enable_timing(False)
     el = max_over_ranks(t1 - t0, dist)
     value = S * F * args.steps * world / el
+    dump_batch_outputs(args, rank, world, b, 0, S)
     verified, vdetail = (None, None) if args.no_verify else \
         verify_splice_step(b, ext_host, wl, first, args.warmup + args.steps)
     if rank == 0:
@@ -886,7 +947,15 @@ def main():
                     help="skip the post-timing oracle check of the last step")
     ap.add_argument("--no-host", action="store_true",
                     help="skip the host-delivery (PCIe-inclusive) and single-frame latency legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline, the oracle check of the "
+                         "last step and the host-delivery / latency legs (each can be switched off "
+                         "with its --no-* option); without it only the headline figure is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_verify = args.no_host = True
 
     wl = dict(WORKLOADS[args.workload])
     if args.streams:
@@ -972,6 +1041,7 @@ def main():
     frames_total = S * F * args.steps * world
     value = frames_total / el
     ms_step = 1000.0 * el / args.steps
+    dump_batch_outputs(args, rank, world, b, 0, S)
 
     # after the timed region: the last step's bytes of this rank's streams
     # against the CPU oracle (the checker), every rank its own shard

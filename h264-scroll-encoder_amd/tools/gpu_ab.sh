@@ -13,6 +13,6 @@ if [ -n "${GPU_AB_TESTS:-}" ]; then
     timeout -k 10 400 python3 -u -m pytest $GPU_AB_TESTS -x -v --timeout 240 --timeout-method thread > "$O/tests.log" 2>&1
 fi
 if [ "${GPU_AB_BENCH:-0}" = 1 ]; then
-    timeout -k 10 300 python3 bench.py > "$O/bench.json" 2> "$O/bench.err"
+    timeout -k 10 300 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err"
 fi
 bash h264-scroll-encoder_amd/tools/abl_sq.sh "$O" "$@"

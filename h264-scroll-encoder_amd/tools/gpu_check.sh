@@ -13,5 +13,5 @@ REV=$(cat .revision 2>/dev/null | tr '\n' ' ')
 for f in gpu_tests.log smoke.log; do echo "revision: $REV" > "$O/$f"; done
 timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread >> "$O/gpu_tests.log" 2>&1
 timeout -k 10 180 python3 -c "import __graft_entry__ as g; g.smoke()" >> "$O/smoke.log" 2>&1
-timeout -k 10 300 python3 bench.py > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 300 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err"
 echo "revision: $REV" > "$O/DONE"

@@ -7,7 +7,7 @@ set -e -o pipefail
 O=$1; mkdir -p "$O"; export TMPDIR=/tmp
 run() { # name lib env...
     local nm=$1 lib=$2; shift 2
-    env "$@" H264SCROLL_LIB=$lib timeout -k 10 200 python3 bench.py --steps 20 --warmup 3 --no-cpu --no-host --workload ipcm720 > "$O/$nm.json" 2> "$O/$nm.err"
+    env "$@" H264SCROLL_LIB=$lib timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 3 --no-cpu --no-host --workload ipcm720 > "$O/$nm.json" 2> "$O/$nm.err"
 }
 for rep in 1 2; do
     run cur_$rep ""

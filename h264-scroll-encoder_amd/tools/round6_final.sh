@@ -10,8 +10,8 @@ REV=$(cat .revision 2>/dev/null | tr '\n' ' ')
 echo "revision: $REV" > "$O/REVISION"
 timeout -k 10 700 python -u -m pytest tests -x -v -m gpu --timeout 120 --timeout-method thread > "$O/gpu_tests.log" 2>&1
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$O/smoke.log" 2>&1
-timeout -k 10 300 python3 bench.py > "$O/bench_p720dyn.json" 2> "$O/bench_p720dyn.err"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats_default" -o run -- python3 bench.py > "$O/stats_default.log" 2>&1
+timeout -k 10 300 python3 bench.py --full > "$O/bench_p720dyn.json" 2> "$O/bench_p720dyn.err"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats_default" -o run -- python3 bench.py --full > "$O/stats_default.log" 2>&1
 bash h264-scroll-encoder_amd/tools/sq_pass.sh "$O/sq_p720dyn"
 SQ_WORKLOAD=p4kdyn bash h264-scroll-encoder_amd/tools/sq_pass.sh "$O/sq_p4kdyn"
 bash h264-scroll-encoder_amd/tools/lds_abl.sh "$O/lds"

@@ -21,12 +21,12 @@ T="timeout -k 10"
 REV=$(cat .revision 2>/dev/null | tr '\n' ' ')
 echo "revision: $REV" > "$O/REVISION_$PART"
 if [ "$PART" = bench ]; then
-    $T 300 python3 bench.py --steps 20 --warmup 3 > "$O/bench_p720dyn.json" 2> "$O/bench_p720dyn.err"
+    $T 300 python3 bench.py --full --steps 20 --warmup 3 > "$O/bench_p720dyn.json" 2> "$O/bench_p720dyn.err"
     for w in p720 p4kdyn p720full p720hint p720splice p720splicerows ingest720 ipcm720; do
-        $T 240 python3 bench.py --steps 10 --warmup 2 --workload $w > "$O/bench_$w.json" 2> "$O/bench_$w.err"
+        $T 240 python3 bench.py --full --steps 10 --warmup 2 --workload $w > "$O/bench_$w.json" 2> "$O/bench_$w.err"
     done
-    $T 200 python3 bench.py --steps 10 --warmup 2 --streams 1024 --no-cpu > "$O/bench_p720dyn_1024streams.json" 2> "$O/bench_p720dyn_1024streams.err"
-    $T 200 python3 bench.py --steps 50 --warmup 5 --frames 1 --no-cpu > "$O/bench_p720dyn_frames1.json" 2> "$O/bench_p720dyn_frames1.err"
+    $T 200 python3 bench.py --full --steps 10 --warmup 2 --streams 1024 --no-cpu > "$O/bench_p720dyn_1024streams.json" 2> "$O/bench_p720dyn_1024streams.err"
+    $T 200 python3 bench.py --full --steps 50 --warmup 5 --frames 1 --no-cpu > "$O/bench_p720dyn_frames1.json" 2> "$O/bench_p720dyn_frames1.err"
 fi
 if [ "$PART" = prof ]; then
     for w in p720dyn p4kdyn p720 p720full p720splicerows ingest720 ipcm720; do

@@ -140,14 +140,14 @@ def test_two_rank_gpu_shards_through_the_library():
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_bench_gpus_2_launches_two_ranks():
-    """python bench.py --gpus 2 with no launcher starts two ranks itself and
+    """python bench.py --gpus 2 --full with no launcher starts two ranks itself and
     prints one line with n_gpus 2 and the verified last step"""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--streams", "16", "--no-cpu"], capture_output=True, text=True,
+                        "--warmup", "1", "--streams", "16", "--full", "--no-cpu"], capture_output=True, text=True,
                        timeout=240, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
