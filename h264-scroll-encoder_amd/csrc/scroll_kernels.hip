@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "dyn_engine.h"
+#include "recon_engine.h"
 #include "hint_engine.h"
 #include "splice_engine.h"
 #include "hdyn_engine.h"
@@ -926,6 +927,12 @@ struct ScrollBatch {
     DynFrame *d_dfr = nullptr;
     uint8_t *d_src = nullptr, *d_refs = nullptr, *d_stage = nullptr;
     DynScratch dx{};                   /* rows, block records, look-back words of the dynamic coder */
+    /* the rect's reconstruction (scroll_batch_set_dyn_recon, recon_kernels.hip) */
+    int recon_on = 0;
+    uint8_t *d_rec = nullptr;          /* decoded rects, d_src's layout and strides          */
+    unsigned long long *d_sse = nullptr;   /* [max_streams * max_frames][3]: Y, Cb, Cr       */
+    hipEvent_t rc_ev[2] = {};          /* timing: around k_dyn_recon (created on first use)  */
+    int rc_timed = 0;                  /* the last compose recorded them                     */
     /* UI hints: staged like the dynamic rect (shares
      * d_dfr, d_stage and geo.slot_bytes; the two are exclusive) */
     int hint_on = 0;
@@ -1142,6 +1149,10 @@ void scroll_batch_destroy(ScrollBatch *b)
     (void)hipFree(b->d_src);
     (void)hipFree(b->d_refs);
     (void)hipFree(b->d_stage);
+    (void)hipFree(b->d_rec);
+    (void)hipFree(b->d_sse);
+    for (hipEvent_t e : b->rc_ev)
+        if (e) (void)hipEventDestroy(e);
     (void)hipFree(b->d_hf);
     (void)hipFree(b->d_pool);
     (void)hipFree(b->d_spf);
@@ -1446,6 +1457,22 @@ static int launch(ScrollBatch *b, int nframes, int plan_mode, int nal_max, hipSt
                 return SCROLL_ERR_HIP;
             }
             if ((rc = mark(6))) return rc;
+            if (b->recon_on) {
+                /* the decoded rects + their squared error, from k_dyn_rows'
+                 * rows on the launch stream (independent of k_dyn_row) */
+                const bool timed = b->timing != 0;
+                if (timed && !b->rc_ev[0]) {
+                    HIPCHK(hipEventCreate(&b->rc_ev[0]));
+                    HIPCHK(hipEventCreate(&b->rc_ev[1]));
+                }
+                if (recon_launch(hs, nframes, S, b->d_st, b->d_nal, b->ld_nal, b->d_pend, b->d_dfr, ld_fr, &G,
+                                 b->dx.rows, b->d_src, b->d_refs, b->d_rec, b->d_sse, b->dx.ctr,
+                                 timed ? b->rc_ev[0] : nullptr, timed ? b->rc_ev[1] : nullptr)) {
+                    set_err("k_dyn_recon launch: %s", hipGetErrorString(hipGetLastError()));
+                    return SCROLL_ERR_HIP;
+                }
+                b->rc_timed = timed ? 1 : 0;
+            }
             if (dyn_launch_pack(hs, nframes, S, b->d_st, b->d_nal, b->ld_nal, b->d_pend, b->d_dfr, ld_fr, &G,
                                 &b->dx, b->d_stage, stamps ? b->d_dbg : nullptr, fk)) {
                 set_err("k_dyn_static / k_dyn_epfix launch: %s", hipGetErrorString(hipGetLastError()));
@@ -1520,6 +1547,13 @@ int scroll_batch_compose_ex(ScrollBatch *b, int nframes, void *hip_stream, int f
     if (b->dyn_pos_custom && !b->hint_on) {
         set_err("scroll_batch_compose: per-frame dynamic rect positions need UI hints "
                 "(scroll_batch_set_hints)");
+        return SCROLL_ERR_CONFIG;
+    }
+    if (b->recon_on && b->hint_on) {
+        /* hints, splices and the fallback code the rect in k_hdyn_code /
+         * k_splice_stage, which k_dyn_recon does not follow */
+        set_err("scroll_batch_compose: the dynamic rect's reconstruction (scroll_batch_set_dyn_recon) "
+                "covers the plain dynamic rect only: clear the hints / splices or turn it off");
         return SCROLL_ERR_CONFIG;
     }
     if (b->hint_on && b->sp_dirty) {
@@ -1901,6 +1935,11 @@ static void dyn_release(ScrollBatch *b)
     (void)hipFree(b->dx.rowstage);
     (void)hipFree(b->dx.ctr);
     (void)hipFree(b->dx.gbits);
+    (void)hipFree(b->d_rec);           /* the reconstruction goes with the rect it was sized for */
+    (void)hipFree(b->d_sse);
+    b->d_rec = nullptr;
+    b->d_sse = nullptr;
+    b->recon_on = 0;
     b->d_src = b->d_refs = nullptr;
     b->dx = DynScratch{};
     b->dyn_on = 0;
@@ -2242,6 +2281,112 @@ int scroll_batch_dyn_totals(ScrollBatch *b, unsigned long long *rbsp_bytes,
     if (ep_bytes) *ep_bytes = e;
     if (dyn_nals) *dyn_nals = n;
     return SCROLL_OK;
+}
+
+/* ------------------- the dynamic rect's reconstruction -------------------- */
+int scroll_batch_set_dyn_recon(ScrollBatch *b, int on)
+{
+    if (!b) return SCROLL_ERR_ARG;
+    if (on && !b->dyn_on) {
+        set_err("scroll_batch_set_dyn_recon: needs a dynamic rect (scroll_batch_set_dyn_rect)");
+        return SCROLL_ERR_CONFIG;
+    }
+    if ((on != 0) == (b->recon_on != 0)) return SCROLL_OK;
+    int rc = batch_host_sync(b);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(b->device));
+    if (!on) {
+        (void)hipFree(b->d_rec);
+        (void)hipFree(b->d_sse);
+        b->d_rec = nullptr;
+        b->d_sse = nullptr;
+        b->recon_on = 0;
+        return SCROLL_OK;
+    }
+    const size_t S = (size_t)b->max_streams, F = (size_t)b->max_frames;
+    hipError_t e = hipMalloc(&b->d_rec, S * b->geo.src_ld);
+    if (e == hipSuccess) e = hipMalloc(&b->d_sse, S * F * 3 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(b->d_rec, 0, S * b->geo.src_ld);
+    if (e == hipSuccess) e = hipMemset(b->d_sse, 0, S * F * 3 * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        set_err("scroll_batch_set_dyn_recon: %s", hipGetErrorString(e));
+        (void)hipFree(b->d_rec);
+        (void)hipFree(b->d_sse);
+        b->d_rec = nullptr;
+        b->d_sse = nullptr;
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory ? SCROLL_ERR_OOM : SCROLL_ERR_HIP;
+    }
+    b->recon_on = 1;
+    b->rc_timed = 0;
+    return SCROLL_OK;
+}
+
+uint8_t *scroll_batch_dyn_recon_device(ScrollBatch *b, size_t *stream_stride, size_t *frame_stride)
+{
+    if (!b || !b->recon_on) return nullptr;
+    if (stream_stride) *stream_stride = b->geo.src_ld;
+    if (frame_stride) *frame_stride = b->geo.src_fr;
+    return b->d_rec;
+}
+
+/* frame f of the last compose: 0 it has a reconstruction, 1 no dynamic NAL,
+ * < 0 not available */
+static int recon_frame(ScrollBatch *b, int s, int f, const char *who)
+{
+    if (!b) return SCROLL_ERR_ARG;
+    if (!b->recon_on) {
+        set_err("%s: the reconstruction is off (scroll_batch_set_dyn_recon)", who);
+        return SCROLL_ERR_CONFIG;
+    }
+    if (s < 0 || s >= b->nstreams || f < 0 || f >= b->last_nframes) {
+        set_err("%s: stream %d / frame %d outside the last compose", who, s, f);
+        return SCROLL_ERR_ARG;
+    }
+    int rc = batch_host_sync(b);
+    if (rc) return rc;
+    DynFrame d;
+    HIPCHK(hipMemcpy(&d, b->d_dfr + (size_t)s * b->max_frames + f, sizeof(d), hipMemcpyDeviceToHost));
+    if (d.nal < 0) return 1;
+    /* DynFrame.err bits DF_OVER | DF_HANDOFF (dyn_kernels.hip): the frame was not coded */
+    if (d.err & 5u) {
+        set_err("%s: stream %d frame %d failed in the dynamic-rect coder: nothing was coded", who, s, f);
+        return SCROLL_ERR_OVERFLOW;
+    }
+    return SCROLL_OK;
+}
+
+int scroll_batch_dyn_recon(ScrollBatch *b, int s, int f, uint8_t *dst)
+{
+    if (!dst) return SCROLL_ERR_ARG;
+    int rc = recon_frame(b, s, f, "scroll_batch_dyn_recon");
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(dst, b->d_rec + (size_t)s * b->geo.src_ld + (size_t)f * b->geo.src_fr, b->geo.src_fr,
+                     hipMemcpyDeviceToHost));
+    return SCROLL_OK;
+}
+
+int scroll_batch_dyn_sse(ScrollBatch *b, int s, int f, uint64_t sse[3])
+{
+    if (!sse) return SCROLL_ERR_ARG;
+    int rc = recon_frame(b, s, f, "scroll_batch_dyn_sse");
+    if (rc) return rc;
+    unsigned long long v[3];
+    HIPCHK(hipMemcpy(v, b->d_sse + ((size_t)s * b->max_frames + f) * 3, sizeof(v), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; ++k) sse[k] = v[k];
+    return SCROLL_OK;
+}
+
+float scroll_batch_dyn_recon_ms(ScrollBatch *b)
+{
+    if (!b || !b->recon_on || !b->rc_timed) return -1.0f;
+    if (batch_host_sync(b)) return -1.0f;
+    float ms = -1.0f;
+    if (hipEventElapsedTime(&ms, b->rc_ev[0], b->rc_ev[1]) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1.0f;
+    }
+    return ms;
 }
 
 /* --------------------------------- UI hints -------------------------------- */

@@ -195,6 +195,13 @@ def _load():
                                                        P(ctypes.c_uint32), P(ctypes.c_uint32)]),
         "scroll_batch_dyn_totals": (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_ulonglong),
                                                    P(ctypes.c_ulonglong), P(ctypes.c_longlong)]),
+        "scroll_batch_set_dyn_recon": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+        "scroll_batch_dyn_recon_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t),
+                                                            P(ctypes.c_size_t)]),
+        "scroll_batch_dyn_recon": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, u8p]),
+        "scroll_batch_dyn_sse": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                P(ctypes.c_uint64)]),
+        "scroll_batch_dyn_recon_ms": (ctypes.c_float, [ctypes.c_void_p]),
         "scroll_batch_kernel_stats_ex": (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_double),
                                                         P(ctypes.c_int)]),
         "scroll_batch_set_hints": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
@@ -685,6 +692,52 @@ class Batch:
         self._chk(lib.scroll_batch_dyn_totals(self.h, ctypes.byref(r), ctypes.byref(e),
                                               ctypes.byref(n)), "dyn_totals")
         return r.value, e.value, n.value
+
+    # ---- the dynamic rect's reconstruction ----
+    def set_dyn_recon(self, on=True):
+        """every compose that follows also produces the decoded rect of each
+        dynamic NAL and its squared error (scroll_batch_set_dyn_recon)"""
+        self._chk(lib.scroll_batch_set_dyn_recon(self.h, 1 if on else 0), "set_dyn_recon")
+
+    def dyn_recon_device(self):
+        """(device pointer, stream stride, frame stride) of the decoded rects"""
+        ls, lf = ctypes.c_size_t(), ctypes.c_size_t()
+        p = lib.scroll_batch_dyn_recon_device(self.h, ctypes.byref(ls), ctypes.byref(lf))
+        return p, ls.value, lf.value
+
+    def dyn_recon(self, s, f):
+        """the decoded rect (384*w*h bytes: Y, Cb, Cr) of frame f of stream s
+        of the last compose, None if it has no dynamic NAL"""
+        n = self.dyn_recon_device()[2]
+        if not n:
+            raise RuntimeError("dyn_recon: the reconstruction is off (set_dyn_recon)")
+        b = u8buf(n)
+        rc = self._chk(lib.scroll_batch_dyn_recon(self.h, s, f, b), "dyn_recon")
+        return None if rc == 1 else bytes(b)
+
+    def dyn_sse(self, s, f):
+        """(Y, Cb, Cr) sums of squared errors of that rect against the source,
+        None if the frame has no dynamic NAL"""
+        v = (ctypes.c_uint64 * 3)()
+        rc = self._chk(lib.scroll_batch_dyn_sse(self.h, s, f, v), "dyn_sse")
+        return None if rc == 1 else (int(v[0]), int(v[1]), int(v[2]))
+
+    def dyn_psnr(self, s, f):
+        """(Y, Cb, Cr) PSNR in dB from dyn_sse and the plane sizes; inf for
+        zero error, None if the frame has no dynamic NAL"""
+        import math
+        sse = self.dyn_sse(s, f)
+        if sse is None:
+            return None
+        n = self.dyn_recon_device()[2]           # 384 w h: 256 luma, 64 + 64 chroma per MB
+        sizes = (n * 2 // 3, n // 6, n // 6)
+        return tuple(math.inf if e == 0 else 10.0 * math.log10(255.0 * 255.0 * m / e)
+                     for e, m in zip(sse, sizes))
+
+    def dyn_recon_ms(self):
+        """with enable_timing: HIP-event ms of the last compose's
+        reconstruction kernels (-1 without)"""
+        return lib.scroll_batch_dyn_recon_ms(self.h)
 
     def last_bytes(self):
         return lib.scroll_batch_last_bytes(self.h)

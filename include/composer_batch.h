@@ -252,6 +252,42 @@ int scroll_batch_dyn_frame_info(ScrollBatch *b, int s, int f, uint32_t *rbsp_byt
 /* last compose, all streams: staged RBSP bytes, EP bytes, dynamic NALs */
 int scroll_batch_dyn_totals(ScrollBatch *b, unsigned long long *rbsp_bytes,
                             unsigned long long *ep_bytes, long long *dyn_nals);
+/* The dynamic rect's reconstruction (opt-in; off: no launch, allocation or
+ * output byte of any compose changes).  With it on, every compose also
+ * produces, for each frame with a dynamic NAL, the rect a decoder displays
+ * -- the coded levels dequantised (H.264 8.5.12.1, chroma DC 8.5.11), inverse
+ * transformed (8.5.12.2), added to the prediction and clipped -- and its sum
+ * of squared errors against the source, per plane.  The emitted bytes are
+ * the same as with it off.
+ *
+ *   scroll_batch_set_dyn_recon(b, on)   needs a dynamic rect
+ *       (SCROLL_ERR_CONFIG without one); allocates the reconstruction
+ *       (sized and laid out like the source buffer) and the error sums;
+ *       on = 0 frees them.  scroll_batch_set_dyn_rect -- a new rect or none
+ *       -- turns it off: call it again for the new rect.
+ *   It covers the plain dynamic rect.  UI hints (the rect in the hint
+ *       record), splices and the fallback code the rect elsewhere: a compose
+ *       with the reconstruction on and hints or splices set fails with
+ *       SCROLL_ERR_CONFIG.
+ *   scroll_batch_dyn_recon_device(b, &ls, &lf)   the device buffer,
+ *       [stream][frame] blocks of 384*w*h bytes at the source's strides
+ *       (luma 16w x 16h, then Cb, Cr 8w x 8h); NULL while off.  Valid on the
+ *       compose's stream after the compose; frames without a dynamic NAL
+ *       keep their earlier bytes.
+ *   scroll_batch_dyn_recon(b, s, f, dst)   frame f of stream s of the last
+ *       compose -> 384*w*h host bytes; scroll_batch_dyn_sse(b, s, f, sse) its
+ *       squared error, Y / Cb / Cr.  Both synchronise the compose's stream.
+ *       0; 1 when the frame has no dynamic NAL (nothing written), as
+ *       scroll_batch_dyn_frame_info; SCROLL_ERR_CONFIG while off,
+ *       SCROLL_ERR_ARG outside the last compose's frames,
+ *       SCROLL_ERR_OVERFLOW for a frame the coder failed.
+ *   scroll_batch_dyn_recon_ms(b)   with scroll_batch_enable_timing: HIP-event
+ *       ms of the reconstruction kernels of the last compose; -1 without. */
+int scroll_batch_set_dyn_recon(ScrollBatch *b, int on);
+uint8_t *scroll_batch_dyn_recon_device(ScrollBatch *b, size_t *stream_stride, size_t *frame_stride);
+int scroll_batch_dyn_recon(ScrollBatch *b, int s, int f, uint8_t *dst);      /* 384*w*h host bytes */
+int scroll_batch_dyn_sse(ScrollBatch *b, int s, int f, uint64_t sse[3]);     /* Y, Cb, Cr */
+float scroll_batch_dyn_recon_ms(ScrollBatch *b);
 /* HIP-event ms of the timed composes since the last call: plan (both
  * passes), emit, dyn stage (= dyn code + dyn pack), dyn emit, dyn code
  * (k_dyn_rows + k_dyn_code), dyn pack (k_dyn_group + k_dyn_ep); accumulators reset
