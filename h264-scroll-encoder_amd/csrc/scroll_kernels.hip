@@ -22,6 +22,7 @@
 
 #include "dyn_engine.h"
 #include "recon_engine.h"
+#include "hrecon_engine.h"
 #include "hint_engine.h"
 #include "splice_engine.h"
 #include "hdyn_engine.h"
@@ -933,6 +934,10 @@ struct ScrollBatch {
     unsigned long long *d_sse = nullptr;   /* [max_streams * max_frames][3]: Y, Cb, Cr       */
     hipEvent_t rc_ev[2] = {};          /* timing: around k_dyn_recon (created on first use)  */
     int rc_timed = 0;                  /* the last compose recorded them                     */
+    /* ... under UI hints (scroll_batch_set_dyn_recon_hinted, hrecon_kernels.hip) */
+    int recon_hinted = 0;
+    int rc_last_hint = 0;              /* the last compose ran k_hdyn_recon                  */
+    std::vector<int> rc_fail;          /* [stream]: the status scroll_batch_sync reported for that compose */
     /* UI hints: staged like the dynamic rect (shares
      * d_dfr, d_stage and geo.slot_bytes; the two are exclusive) */
     int hint_on = 0;
@@ -1420,6 +1425,25 @@ static int launch(ScrollBatch *b, int nframes, int plan_mode, int nal_max, hipSt
                 set_err("k_hdyn_code launch: %s", hipGetErrorString(hipGetLastError()));
                 return SCROLL_ERR_HIP;
             }
+            if (combined && b->recon_on && b->recon_hinted) {
+                /* the decoded rects + their squared error at the hinted
+                 * motion, beside k_hdyn_code (after k_hint_fb: it reads the
+                 * frames' fallback bits) */
+                const bool timed = b->timing != 0;
+                if (timed && !b->rc_ev[0]) {
+                    HIPCHK(hipEventCreate(&b->rc_ev[0]));
+                    HIPCHK(hipEventCreate(&b->rc_ev[1]));
+                }
+                if (hrecon_launch(hs, nframes, S, b->d_st, b->d_nal, b->ld_nal, b->d_pend, b->d_dfr, ld_fr,
+                                  b->d_hf, b->d_pool, b->d_spf, &b->geo, b->d_src, b->d_refs, b->d_rec, b->d_sse,
+                                  timed ? b->rc_ev[0] : nullptr, timed ? b->rc_ev[1] : nullptr)) {
+                    set_err("k_hdyn_recon launch: %s", hipGetErrorString(hipGetLastError()));
+                    return SCROLL_ERR_HIP;
+                }
+                b->rc_timed = timed ? 1 : 0;
+                b->rc_last_hint = 1;
+                std::fill(b->rc_fail.begin(), b->rc_fail.end(), 0);
+            }
             if ((b->sp_n > 0 || combined) &&
                 splice_launch_stage(hs, nframes, S, b->d_st, b->d_nal, b->ld_nal, b->d_pend,
                                     b->d_dfr, ld_fr, b->d_hf, b->d_pool, b->d_spf, b->d_sp_rec,
@@ -1472,6 +1496,7 @@ static int launch(ScrollBatch *b, int nframes, int plan_mode, int nal_max, hipSt
                     return SCROLL_ERR_HIP;
                 }
                 b->rc_timed = timed ? 1 : 0;
+                b->rc_last_hint = 0;
             }
             if (dyn_launch_pack(hs, nframes, S, b->d_st, b->d_nal, b->ld_nal, b->d_pend, b->d_dfr, ld_fr, &G,
                                 &b->dx, b->d_stage, stamps ? b->d_dbg : nullptr, fk)) {
@@ -1550,11 +1575,18 @@ int scroll_batch_compose_ex(ScrollBatch *b, int nframes, void *hip_stream, int f
         return SCROLL_ERR_CONFIG;
     }
     if (b->recon_on && b->hint_on) {
-        /* hints, splices and the fallback code the rect in k_hdyn_code /
-         * k_splice_stage, which k_dyn_recon does not follow */
-        set_err("scroll_batch_compose: the dynamic rect's reconstruction (scroll_batch_set_dyn_recon) "
-                "covers the plain dynamic rect only: clear the hints / splices or turn it off");
-        return SCROLL_ERR_CONFIG;
+        /* hints and the fallback code the rect in k_hdyn_code /
+         * k_splice_stage, which k_dyn_recon does not follow: k_hdyn_recon
+         * does, once opted in; a spliced slice carries MB types neither decodes */
+        bool spliced = b->sp_n > 0;
+        for (const ScrollBatch::SpliceHost &sp : b->h_sp) spliced |= sp.w > 0;
+        if (!b->recon_hinted || spliced) {
+            set_err("scroll_batch_compose: the dynamic rect's reconstruction (scroll_batch_set_dyn_recon) "
+                    "covers the plain dynamic rect, and the rect under UI hints with "
+                    "scroll_batch_set_dyn_recon_hinted, never spliced slices: clear the hints / splices, opt "
+                    "in or turn it off");
+            return SCROLL_ERR_CONFIG;
+        }
     }
     if (b->hint_on && b->sp_dirty) {
         int rc = splice_upload(b);
@@ -1578,6 +1610,22 @@ int scroll_batch_compose_ex(ScrollBatch *b, int nframes, void *hip_stream, int f
                   (flags & SCROLL_COMPOSE_REWIND) ? PLAN_REWIND : 0);
 }
 
+/* the status scroll_batch_sync gives for stream s's pending error bits */
+static int stream_fail_code(ScrollBatch *b, int s)
+{
+    const int32_t e = b->h_st[s].err;
+    if (!e) return SCROLL_OK;
+    if (e & SCROLL_DEVERR_HANDOFF) return SCROLL_ERR_DEVICE;
+    if (e & SCROLL_DEVERR_SPLICE) {
+        int st = 0;
+        for (int ff = 0; ff < b->max_frames && !st; ++ff)
+            if (splice_frame_status(b, (size_t)s * b->max_frames + ff, &st)) break;
+        return st == HDYN_STATUS_OVERFLOW ? SCROLL_ERR_OVERFLOW : SCROLL_ERR_CONFIG;
+    }
+    if (e & SCROLL_DEVERR_HINT) return SCROLL_ERR_CONFIG;
+    return SCROLL_ERR_OVERFLOW;
+}
+
 int scroll_batch_sync(ScrollBatch *b)
 {
     if (!b) return SCROLL_ERR_ARG;
@@ -1593,6 +1641,8 @@ int scroll_batch_sync(ScrollBatch *b)
     int rc = SCROLL_OK;
     for (int s = 0; s < b->nstreams; ++s) {
         if (!b->h_st[s].err) continue;
+        if (b->rc_last_hint && (size_t)s < b->rc_fail.size())
+            b->rc_fail[s] = stream_fail_code(b, s);
         if (rc == SCROLL_OK && (b->h_st[s].err & SCROLL_DEVERR_HANDOFF)) {
             set_err("stream %d: a dynamic-rect row waited past its bound for the row above's "
                     "TotalCoeffs (k_dyn_row hand-off); the stream committed nothing", s);
@@ -1940,6 +1990,7 @@ static void dyn_release(ScrollBatch *b)
     b->d_rec = nullptr;
     b->d_sse = nullptr;
     b->recon_on = 0;
+    b->recon_hinted = 0;
     b->d_src = b->d_refs = nullptr;
     b->dx = DynScratch{};
     b->dyn_on = 0;
@@ -2301,6 +2352,7 @@ int scroll_batch_set_dyn_recon(ScrollBatch *b, int on)
         b->d_rec = nullptr;
         b->d_sse = nullptr;
         b->recon_on = 0;
+        b->recon_hinted = 0;
         return SCROLL_OK;
     }
     const size_t S = (size_t)b->max_streams, F = (size_t)b->max_frames;
@@ -2319,6 +2371,21 @@ int scroll_batch_set_dyn_recon(ScrollBatch *b, int on)
     }
     b->recon_on = 1;
     b->rc_timed = 0;
+    b->rc_last_hint = 0;
+    return SCROLL_OK;
+}
+
+int scroll_batch_set_dyn_recon_hinted(ScrollBatch *b, int on)
+{
+    if (!b) return SCROLL_ERR_ARG;
+    if (on && !b->recon_on) {
+        set_err("scroll_batch_set_dyn_recon_hinted: needs the reconstruction on (scroll_batch_set_dyn_recon)");
+        return SCROLL_ERR_CONFIG;
+    }
+    int rc = batch_host_sync(b);
+    if (rc) return rc;
+    if (on) b->rc_fail.resize((size_t)b->max_streams, 0);   /* sized here, not on the compose path */
+    b->recon_hinted = on ? 1 : 0;
     return SCROLL_OK;
 }
 
@@ -2345,8 +2412,27 @@ static int recon_frame(ScrollBatch *b, int s, int f, const char *who)
     }
     int rc = batch_host_sync(b);
     if (rc) return rc;
+    const size_t fi = (size_t)s * b->max_frames + f;
     DynFrame d;
-    HIPCHK(hipMemcpy(&d, b->d_dfr + (size_t)s * b->max_frames + f, sizeof(d), hipMemcpyDeviceToHost));
+    if (b->rc_last_hint) {
+        /* a hinted compose: a stream that failed has no reconstruction to
+         * show (its error bits, or what scroll_batch_sync made of them) */
+        const int e = b->h_st[s].err ? stream_fail_code(b, s) : ((size_t)s < b->rc_fail.size() ? b->rc_fail[s] : 0);
+        if (e) {
+            set_err("%s: stream %d failed in the last compose (status %d): no reconstruction", who, s, e);
+            return e;
+        }
+        HIPCHK(hipMemcpy(&d, b->d_dfr + fi, sizeof(d), hipMemcpyDeviceToHost));
+        if (d.nal < 0 || !b->d_spf || !b->d_hf) return 1;
+        SpliceFrame sf;
+        HintFrame hfr;
+        HIPCHK(hipMemcpy(&sf, b->d_spf + fi, sizeof(sf), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&hfr, b->d_hf + fi, sizeof(hfr), hipMemcpyDeviceToHost));
+        /* no rect in the frame, or a dormant fallback region in a frame that did not fall back */
+        if (sf.w <= 0 || ((sf.pad & 1) && !(hfr.mode & HINT_MODE_FB))) return 1;
+        return SCROLL_OK;
+    }
+    HIPCHK(hipMemcpy(&d, b->d_dfr + fi, sizeof(d), hipMemcpyDeviceToHost));
     if (d.nal < 0) return 1;
     /* DynFrame.err bits DF_OVER | DF_HANDOFF (dyn_kernels.hip): the frame was not coded */
     if (d.err & 5u) {

@@ -196,6 +196,7 @@ def _load():
         "scroll_batch_dyn_totals": (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_ulonglong),
                                                    P(ctypes.c_ulonglong), P(ctypes.c_longlong)]),
         "scroll_batch_set_dyn_recon": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+        "scroll_batch_set_dyn_recon_hinted": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
         "scroll_batch_dyn_recon_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t),
                                                             P(ctypes.c_size_t)]),
         "scroll_batch_dyn_recon": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, u8p]),
@@ -694,10 +695,14 @@ class Batch:
         return r.value, e.value, n.value
 
     # ---- the dynamic rect's reconstruction ----
-    def set_dyn_recon(self, on=True):
+    def set_dyn_recon(self, on=True, hinted=False):
         """every compose that follows also produces the decoded rect of each
-        dynamic NAL and its squared error (scroll_batch_set_dyn_recon)"""
+        dynamic NAL and its squared error (scroll_batch_set_dyn_recon);
+        hinted: composes with UI hints too, the rect at its hinted motion
+        (scroll_batch_set_dyn_recon_hinted) -- without it they are refused"""
         self._chk(lib.scroll_batch_set_dyn_recon(self.h, 1 if on else 0), "set_dyn_recon")
+        if on:
+            self._chk(lib.scroll_batch_set_dyn_recon_hinted(self.h, 1 if hinted else 0), "set_dyn_recon_hinted")
 
     def dyn_recon_device(self):
         """(device pointer, stream stride, frame stride) of the decoded rects"""

@@ -13,13 +13,20 @@ stream), one JSON line:
                    of the library (the parent revision's), in the same
                    rounds -- the reconstruction off must cost nothing, so the
                    pair is judged by its run-to-run spread;
-  recon_kernel_ms  k_dyn_recon alone, by the batch's HIP events around it;
+  recon_kernel_ms  k_dyn_recon (--hinted: k_hdyn_recon) alone, by the batch's
+                   HIP events around it;
   alg_bytes        its algorithmic bytes: dynamic NALs x rect MBs x 1152
                    (384 B of source and of prediction read, 384 B written);
   hbm_frac         alg_bytes / time against bench.py's HBM peak.
 
+--hinted: the same batch with UI hints on -- one hint band (ref 0, a
+horizontal motion) crossing the rect in every frame, SCROLL_HINT_PSKIP -- so
+the rect is coded by k_hdyn_code / k_splice_stage and reconstructed by
+k_hdyn_recon (scroll_batch_set_dyn_recon_hinted).
+
 Usage: python h264-scroll-encoder_amd/tools/recon_bench.py [--rounds 7]
        [--steps 10] [--streams 256] [--frames 16] [--parent-lib PATH]
+       [--hinted]
 """
 import argparse
 import importlib.util
@@ -65,6 +72,8 @@ def main():
     ap.add_argument("--frames", type=int, default=0)
     ap.add_argument("--parent-lib", default=None, help="libh264scroll.so of the revision to compare the "
                                                        "reconstruction-off step with")
+    ap.add_argument("--hinted", action="store_true", help="UI hints on: one band crossing the rect per frame, "
+                                                          "PSKIP (k_hdyn_code + k_hdyn_recon)")
     args = ap.parse_args()
 
     import torch
@@ -99,6 +108,13 @@ def main():
             raise RuntimeError(mod.last_error())
         return e0.elapsed_time(e1) / n
 
+    if args.hinted:
+        mbw = wl["w"] // 16
+        for mod, bb in arms.values():
+            for s in range(S):
+                for f in range(F):
+                    y = rect[1] + (3 * s + f) % rect[3]
+                    bb.set_hints(s, f, [(0, y, mbw, y + 2, 0, 8 * (f % 5) - 13, 0)], mod.SCROLL_HINT_PSKIP)
     b = arms["off"][1]
     times = {k: [] for k in list(arms) + ["on"]}
     out_bytes = {}
@@ -108,14 +124,14 @@ def main():
         for k, (mod, bb) in arms.items():
             times[k].append(block(mod, bb, args.steps))
             out_bytes[k] = bb.last_bytes()
-        b.set_dyn_recon(True)
+        b.set_dyn_recon(True, hinted=args.hinted)
         block(hs, b, 1)
         times["on"].append(block(hs, b, args.steps))
         out_bytes["on"] = b.last_bytes()
         b.set_dyn_recon(False)
 
     # the kernel alone: the batch's own event pair around it
-    b.set_dyn_recon(True)
+    b.set_dyn_recon(True, hinted=args.hinted)
     b.enable_timing(True, lite=True)
     kern = []
     for _ in range(max(args.rounds, 5)):
@@ -138,7 +154,8 @@ def main():
     achieved = alg / (kms * 1e-3) / 1e9
     out = {
         "tool": "recon_bench",
-        "config": {"workload": "BASELINE config 3", "resolution": f"{wl['w']}x{wl['h']}", "streams": S,
+        "config": {"workload": "BASELINE config 3" + (" + UI hints (one band over the rect, PSKIP)" if args.hinted
+                                                      else ""), "resolution": f"{wl['w']}x{wl['h']}", "streams": S,
                    "frames_per_step": F, "rect": list(rect), "source": "synthetic (k_dyn_synth)"},
         "timing": f"{args.rounds} interleaved rounds, {args.steps} composes per block between two HIP events",
         "step_ms": {k: spread(v) for k, v in times.items()},

@@ -265,10 +265,25 @@ int scroll_batch_dyn_totals(ScrollBatch *b, unsigned long long *rbsp_bytes,
  *       (sized and laid out like the source buffer) and the error sums;
  *       on = 0 frees them.  scroll_batch_set_dyn_rect -- a new rect or none
  *       -- turns it off: call it again for the new rect.
- *   It covers the plain dynamic rect.  UI hints (the rect in the hint
- *       record), splices and the fallback code the rect elsewhere: a compose
- *       with the reconstruction on and hints or splices set fails with
- *       SCROLL_ERR_CONFIG.
+ *   By itself it covers the plain dynamic rect: a compose with the
+ *       reconstruction on and UI hints set fails with SCROLL_ERR_CONFIG.
+ *   scroll_batch_set_dyn_recon_hinted(b, on)   opt-in on top of it (needs the
+ *       reconstruction on, SCROLL_ERR_CONFIG otherwise; off by default;
+ *       set_dyn_recon(b, 0) and set_dyn_rect turn it off too): composes with
+ *       UI hints -- the rect in the hint record, per-frame positions
+ *       (set_dyn_rect_at) and QPs (set_dyn_qp_at), the whole-picture fallback
+ *       -- then fill the same two outputs for every frame whose rect was
+ *       coded, each MB predicted at its hinted motion (full-pel luma, 2-D
+ *       1/8-pel chroma, samples clamped to the picture) and quantised at the
+ *       frame's QP.  Composes without hints on such a batch are unchanged.
+ *       Spliced slices stay refused (SCROLL_ERR_CONFIG): they carry MB types
+ *       the reconstruction does not decode.  Under hints the accessors below
+ *       return 1 for a frame without a dynamic NAL, without the rect
+ *       (set_dyn_rect_at with x0 = -1) or with a fallback region that did not
+ *       fall back, and the stream's negative compose status (what
+ *       scroll_batch_sync reports for it: SCROLL_ERR_CONFIG for a hint on a
+ *       missing reference, SCROLL_ERR_OVERFLOW for an MB past its region)
+ *       for every frame of a stream whose last compose failed.
  *   scroll_batch_dyn_recon_device(b, &ls, &lf)   the device buffer,
  *       [stream][frame] blocks of 384*w*h bytes at the source's strides
  *       (luma 16w x 16h, then Cb, Cr 8w x 8h); NULL while off.  Valid on the
@@ -284,6 +299,7 @@ int scroll_batch_dyn_totals(ScrollBatch *b, unsigned long long *rbsp_bytes,
  *   scroll_batch_dyn_recon_ms(b)   with scroll_batch_enable_timing: HIP-event
  *       ms of the reconstruction kernels of the last compose; -1 without. */
 int scroll_batch_set_dyn_recon(ScrollBatch *b, int on);
+int scroll_batch_set_dyn_recon_hinted(ScrollBatch *b, int on);
 uint8_t *scroll_batch_dyn_recon_device(ScrollBatch *b, size_t *stream_stride, size_t *frame_stride);
 int scroll_batch_dyn_recon(ScrollBatch *b, int s, int f, uint8_t *dst);      /* 384*w*h host bytes */
 int scroll_batch_dyn_sse(ScrollBatch *b, int s, int f, uint64_t sse[3]);     /* Y, Cb, Cr */
