@@ -34,6 +34,7 @@
 
 #include "dyn_device.h"
 #include "dyn_engine.h"
+#include "nal_ctx.h"
 #include "row_mfma.h"
 #include "stage_util.h"
 
@@ -211,27 +212,6 @@ __device__ inline void flush_window(const uint32_t *buf, uint32_t n, uint32_t p0
 }
 
 __device__ inline uint32_t ld32(const uint8_t *p) { return *reinterpret_cast<const uint32_t *>(p); }
-
-/* NalCtx of scroll NAL d of stream S with the waypoint table (wo, wl, wv) */
-__device__ inline NalCtx nal_ctx(const DevStream *S, const NalDesc &d, const int32_t *wo, const int32_t *wl,
-                                 const int32_t *wv)
-{
-    NalCtx c;
-    c.w = S->w;
-    c.h = S->h;
-    c.log2_mfn = S->log2_mfn;
-    c.poc_type = S->poc_type;
-    c.log2_poc = S->log2_poc;
-    c.deblock = S->deblock;
-    c.kind = d.kind;
-    c.off = d.off;
-    c.frame_num = d.frame_num;
-    c.nwp = d.nwp;
-    c.wp_off = wo;
-    c.wp_lt = wl;
-    c.wp_valid = wv;
-    return c;
-}
 
 /* ====================================================================== */
 /* Pieces of dynamic MB q (rect raster order): pc 0..15 luma 4x4 (raster),  */

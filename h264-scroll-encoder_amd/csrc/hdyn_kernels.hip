@@ -32,6 +32,7 @@
 #include "dyn_device.h"
 #include "hdyn_engine.h"
 #include "hint_device.h"
+#include "nal_ctx.h"
 #include "splice_engine.h"
 #include "stage_util.h"
 
@@ -118,22 +119,8 @@ __global__ __launch_bounds__(HD_T) void k_hdyn_code(const DevStream *__restrict_
     lds_wave_sync();
     const DevStream *S = st + s;
     const NalDesc d = nal[(size_t)s * ld_nal + df.nal];
-    NalCtx c;
-    c.w = S->w;
-    c.h = S->h;
-    c.log2_mfn = S->log2_mfn;
-    c.poc_type = S->poc_type;
-    c.log2_poc = S->log2_poc;
-    c.deblock = S->deblock;
-    c.kind = d.kind;
-    c.off = d.off;
-    c.frame_num = d.frame_num;
-    c.nwp = d.nwp;
-    c.wp_off = L.wo;
-    c.wp_lt = L.wl;
-    c.wp_valid = L.wv;
-    const Regions rg = regions(c);
-    const Layout lay{(c.h - c.off) / 16, rg.ra, 4 * rg.mva, rg.rb, 4 * rg.mvb};
+    const NalCtx c = nal_ctx(S, d, L.wo, L.wl, L.wv);
+    const Layout lay = layout(c);
     const int lx = q % SF.w, ly = q / SF.w, x = SF.x0 + lx, y = SF.y0 + ly;
     bool bad;
     const Mv me = field(L.rc, L.wv, nr, x, y, lay, c.nwp, bad);

@@ -1,6 +1,7 @@
 /*
  * hint_device.h -- motion of a hinted / spliced frame, shared by k_hint_stage
- * (hint_kernels.hip) and k_splice_stage (splice_kernels.hip): the MV field
+ * (hint_kernels.hip), k_splice_stage (splice_kernels.hip), k_hdyn_code
+ * (hdyn_kernels.hip) and k_hdyn_recon (hrecon_kernels.hip): the MV field
  * of the UI hints over the scroll layout, the reference's predictor
  * (h264_writer.c:369-432), the standard's (H.264 8.4.1.3) and P_Skip motion
  * (8.4.1.1).  Bits: oracle/hint_oracle.c.
@@ -26,6 +27,12 @@ struct Mv {
 struct Layout {
     int a_end, ra, mva4, rb, mvb4;
 };
+/* of the NAL whose context is c (its waypoint pointers set: regions() reads them) */
+__device__ inline Layout layout(const NalCtx &c)
+{
+    const Regions rg = regions(c);
+    return Layout{(c.h - c.off) / 16, rg.ra, 4 * rg.mva, rg.rb, 4 * rg.mvb};
+}
 
 /* the MB's own motion: the topmost rect holding it, else its scroll row;
  * bad = the rect names no valid reference of the frame */

@@ -30,6 +30,7 @@
 #include "dyn_device.h"
 #include "hint_device.h"
 #include "hint_engine.h"
+#include "nal_ctx.h"
 #include "splice_engine.h"
 #include "stage_util.h"
 
@@ -93,20 +94,7 @@ __global__ __launch_bounds__(DT) void k_hint_stage(DevStream *__restrict__ st,
     if (t < nr) L.rc[t] = pool[H.first + t];
     for (int i = t; i < HB_WORDS; i += DT) L.buf[i] = 0u;
     const NalDesc d = nal[(size_t)s * ld_nal + j];
-    NalCtx c;
-    c.w = S->w;
-    c.h = S->h;
-    c.log2_mfn = S->log2_mfn;
-    c.poc_type = S->poc_type;
-    c.log2_poc = S->log2_poc;
-    c.deblock = S->deblock;
-    c.kind = d.kind;
-    c.off = d.off;
-    c.frame_num = d.frame_num;
-    c.nwp = d.nwp;
-    c.wp_off = L.wo;
-    c.wp_lt = L.wl;
-    c.wp_valid = L.wv;
+    const NalCtx c = nal_ctx(S, d, L.wo, L.wl, L.wv);
     __syncthreads();
 
     /* slice header (h264_writer.c:549-553): thread 0 writes, all count */
@@ -123,8 +111,7 @@ __global__ __launch_bounds__(DT) void k_hint_stage(DevStream *__restrict__ st,
         }
     }
     const int mbw = c.w / 16, mbh = c.h / 16, nmb = mbw * mbh;
-    const Regions rg = regions(c);
-    const Layout lay{(c.h - c.off) / 16, rg.ra, 4 * rg.mva, rg.rb, 4 * rg.mvb};
+    const Layout lay = layout(c);
     const int nrefs = 2 + c.nwp;
     const uint32_t m_mbw = magic32((uint32_t)mbw);
     uint8_t *slot = stage + ((size_t)s * ld_fr + f) * slot_bytes;
@@ -292,25 +279,14 @@ __global__ __launch_bounds__(DT) void k_hint_fb(const DevStream *__restrict__ st
         if (t == 0) any = 0;
         __syncthreads();
         const DevStream *S = st + s;
-        const NalDesc d = nal[(size_t)s * ld_nal + j];
-        NalCtx c;
-        c.w = S->w;
-        c.h = S->h;
-        c.log2_mfn = S->log2_mfn;
-        c.poc_type = S->poc_type;
-        c.log2_poc = S->log2_poc;
-        c.deblock = S->deblock;
-        c.kind = d.kind;
-        c.off = d.off;
-        c.frame_num = d.frame_num;
-        c.nwp = d.nwp;
-        const Regions rg = regions(c);
-        const Layout lay{(c.h - c.off) / 16, rg.ra, 4 * rg.mva, rg.rb, 4 * rg.mvb};
-        const int mbw = c.w / 16, nmb = mbw * (c.h / 16);
+        const int nwp = nal[(size_t)s * ld_nal + j].nwp;
+        const int mbw = S->w / 16, nmb = mbw * (S->h / 16);
         bool my = false;
         for (int m = t; m < nmb; m += DT) {
             bool b1;
-            (void)field(rc, wv, nr, m % mbw, m / mbw, lay, c.nwp, b1);
+            /* only the rects' references matter: the motion, and with it the
+             * scroll layout under the rects, is not looked at */
+            (void)field(rc, wv, nr, m % mbw, m / mbw, Layout{}, nwp, b1);
             my |= b1;
         }
         if (my) any = 1;

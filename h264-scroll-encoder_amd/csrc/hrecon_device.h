@@ -31,30 +31,7 @@ using dyn::clampi;
 using dyn::luma_row;
 using dyn::RefPics;
 using dyn::WpTab;
-
-/* the stream's two reference pictures, I420 one after the other (plane
- * addresses by arithmetic: a pointer table indexed by the picture a row
- * resolves to would live in scratch) */
-struct Pics {
-    const uint8_t *base;
-    int w, h;
-    __device__ __host__ inline uint32_t ysz() const { return (uint32_t)w * (uint32_t)h; }
-    /* plane p (0 Y, 1 Cb, 2 Cr) of picture b */
-    __device__ __host__ inline const uint8_t *plane(int b, int p) const
-    {
-        const uint32_t y = ysz();
-        return base + (size_t)b * (y + y / 2) + (p == 0 ? 0u : p == 1 ? y : y + y / 4);
-    }
-    __device__ __host__ inline RefPics refpics() const
-    {
-        RefPics R;
-        for (int b = 0; b < 2; ++b)
-            for (int p = 0; p < 3; ++p) R.pl[b][p] = plane(b, p);
-        R.w = w;
-        R.h = h;
-        return R;
-    }
-};
+using recon::Pics;
 
 /* bytes X .. X + n - 1 (n <= 5) of a row from the aligned dwords that hold
  * them: needs 0 <= X and X + n <= the row's length.  The second dword is

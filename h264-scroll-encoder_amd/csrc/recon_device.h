@@ -7,7 +7,8 @@
  * quant_dc, QParams, +-LEVEL_MAX clamp and QPc (dyn_device.h).  This header
  * adds the decoder's half: dequantisation with flat scaling lists
  * (H.264 8.5.12.1), the chroma DC path (8.5.11.1 / 8.5.11.2), the inverse
- * 4x4 transform (8.5.12.2), prediction + clip.
+ * 4x4 transform (8.5.12.2), prediction + clip; and where the prediction is
+ * read from: the addresses of a stream's reference planes (Pics).
  *
  * Pure integer functions like dyn_device.h: k_dyn_recon (recon_kernels.hip)
  * uses them per lane, tests/hostsim/recon_sim.cpp compiles them for the CPU
@@ -22,6 +23,30 @@ namespace scroll {
 namespace recon {
 
 using dyn::clampi;
+
+/* the stream's two reference pictures, I420 one after the other (plane
+ * addresses by arithmetic: a pointer table indexed by the picture a row
+ * resolves to would live in scratch) */
+struct Pics {
+    const uint8_t *base;
+    int w, h;
+    __device__ __host__ inline uint32_t ysz() const { return (uint32_t)w * (uint32_t)h; }
+    /* plane p (0 Y, 1 Cb, 2 Cr) of picture b */
+    __device__ __host__ inline const uint8_t *plane(int b, int p) const
+    {
+        const uint32_t y = ysz();
+        return base + (size_t)b * (y + y / 2) + (p == 0 ? 0u : p == 1 ? y : y + y / 4);
+    }
+    __device__ __host__ inline dyn::RefPics refpics() const
+    {
+        dyn::RefPics R;
+        for (int b = 0; b < 2; ++b)
+            for (int p = 0; p < 3; ++p) R.pl[b][p] = plane(b, p);
+        R.w = w;
+        R.h = h;
+        return R;
+    }
+};
 
 /* LevelScale / 16 of the (even, even) / (odd, odd) / mixed 4x4 positions at
  * QP % 6 (Table of 8.5.9, v), shift = QP / 6: the position classes of

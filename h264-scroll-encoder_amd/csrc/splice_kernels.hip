@@ -36,6 +36,7 @@
 
 #include "dyn_device.h"
 #include "hint_device.h"
+#include "nal_ctx.h"
 #include "splice_engine.h"
 #include "stage_util.h"
 
@@ -2309,20 +2310,7 @@ __global__ __launch_bounds__(DT) __attribute__((amdgpu_waves_per_eu(SCROLL_STAGE
     build_ptabs(SPT, L.pt, t, DT);
     if (t < 48) L.cbpc[t] = SPT.cbp_code[t];
     const NalDesc d = nal[(size_t)s * ld_nal + j];
-    NalCtx c;
-    c.w = S->w;
-    c.h = S->h;
-    c.log2_mfn = S->log2_mfn;
-    c.poc_type = S->poc_type;
-    c.log2_poc = S->log2_poc;
-    c.deblock = S->deblock;
-    c.kind = d.kind;
-    c.off = d.off;
-    c.frame_num = d.frame_num;
-    c.nwp = d.nwp;
-    c.wp_off = L.wo;
-    c.wp_lt = L.wl;
-    c.wp_valid = L.wv;
+    const NalCtx c = nal_ctx(S, d, L.wo, L.wl, L.wv);
     __syncthreads();
 
     uint32_t F0;
@@ -2332,8 +2320,7 @@ __global__ __launch_bounds__(DT) __attribute__((amdgpu_waves_per_eu(SCROLL_STAGE
         F0 = hc.n;
     }
     const int mbw = c.w / 16, mbh = c.h / 16, nmb = mbw * mbh;
-    const Regions rg = regions(c);
-    const Layout lay{(c.h - c.off) / 16, rg.ra, 4 * rg.mva, rg.rb, 4 * rg.mvb};
+    const Layout lay = layout(c);
     const int nrefs = 2 + c.nwp;
     const uint32_t m_mbw = magic32((uint32_t)mbw);
     uint8_t *slot = stage + fi * slot_bytes;

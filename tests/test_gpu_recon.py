@@ -130,11 +130,13 @@ def test_clipping(gpu, oracle):
     b.close()
 
 
-@pytest.mark.parametrize("rect", [(0, 1, 12, 2), (11, 0, 1, 4)])
+@pytest.mark.parametrize("rect", [(0, 1, 12, 2), (11, 0, 1, 4), (0, 1, 17, 2)])
 def test_row_loop_and_widths(gpu, oracle, rect):
     """12 MBs wide: 288 blocks per rect row, more than the workgroup's 256
-    (the row loops); one MB wide at the right picture edge"""
-    w, h = 192, 64
+    (the row loops); one MB wide at the right picture edge; 17 MBs wide (a
+    272 x 64 picture): 34 chroma blocks per row, a second, partly filled
+    chroma wave per plane"""
+    w, h = max(192, 16 * (rect[0] + rect[2])), 64
     run_case(gpu, oracle, w, h, rect, [[3, 30]], random_refs(w, h, 41))
 
 
