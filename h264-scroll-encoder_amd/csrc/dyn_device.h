@@ -1369,6 +1369,9 @@ __device__ __host__ inline int blk_raster(int blk)
     return 4 * ((q8 >> 1) * 2 + (q4 >> 1)) + (q8 & 1) * 2 + (q4 & 1);
 }
 
+/* bits of ue(v), v < 2^31 - 1 */
+__device__ __host__ inline uint32_t ue_bits(uint32_t v) { return 2u * (31u - (uint32_t)__builtin_clz(v + 1u)) + 1u; }
+
 /* ---------------------------------------------------------------------- */
 /* MB order inside a NAL with the rect                                     */
 /* ---------------------------------------------------------------------- */

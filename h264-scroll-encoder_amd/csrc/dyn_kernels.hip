@@ -700,6 +700,36 @@ __device__ inline void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+/* v of the lane dpp_ctrl names, 0 where that lane is outside the row or the
+ * row is not in row_mask */
+template <int CTRL, int ROWS>
+__device__ inline uint32_t dpp_or0(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xf, false);
+}
+
+/* inclusive prefix sum inside each aligned group of 32 lanes, on the DPP
+ * path (no LDS crossbar): four shifts inside the rows of 16 lanes
+ * (row_shr:1 / 2 / 4 / 8), then lane 15 of rows 0 and 2 into every lane of
+ * rows 1 and 3 (row_bcast:15).  Every lane of the wave is active. */
+__device__ inline uint32_t seg32_incl_sum(uint32_t v)
+{
+    v += dpp_or0<0x111, 0xf>(v);
+    v += dpp_or0<0x112, 0xf>(v);
+    v += dpp_or0<0x114, 0xf>(v);
+    v += dpp_or0<0x118, 0xf>(v);
+    v += dpp_or0<0x142, 0xa>(v);
+    return v;
+}
+
+/* the same over the whole wave: lane 31 into rows 2 and 3 (row_bcast:31) */
+__device__ inline uint32_t wave_incl_sum_dpp(uint32_t v)
+{
+    v = seg32_incl_sum(v);
+    v += dpp_or0<0x143, 0xc>(v);
+    return v;
+}
+
 /* a > 128-bit block from its levels (rare): measure / write.  bd: 16 int8
  * levels (chroma DC: 4 int16); bw != nullptr: the 16-bit form of the
  * general path below QP_MIN -- bd levels 0-7, *bw levels 8-15, int16 */
@@ -2024,45 +2054,19 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             }
             lb_store(tcx + (nb * R.h + r) * (size_t)w + t, (uint64_t)(epoch & 0xffffffu) << 40 | v);
         }
-        /* chroma DC blocks, whole (nC = -1) */
-        if (t >= T - 2 * w) {
-            const int i = t - (T - 2 * w), k = i >> 1, p = i & 1, sl = k * NPC + 16 + p;
-            const uint4 q = lv[sl];
-#ifdef SCROLL_ROW_OLDREC
-            const int dq[4] = {(int)(int16_t)(q.x & 0xffffu), (int)(int16_t)(q.x >> 16),
-                               (int)(int16_t)(q.y & 0xffffu), (int)(int16_t)(q.y >> 16)};
-#else
-            /* the four DC coefficients of the plane's 4x4 blocks (raster) ->
-             * 2x2 Hadamard, quant (qbits + 1) */
-            const int d0 = (int)(int16_t)(q.x & 0xffffu), d1 = (int)(int16_t)(q.x >> 16);
-            const int d2 = (int)(int16_t)(q.y & 0xffffu), d3 = (int)(int16_t)(q.y >> 16);
-            const int dq[4] = {quant_dc(d0 + d1 + d2 + d3, qc), quant_dc(d0 - d1 + d2 - d3, qc),
-                               quant_dc(d0 + d1 - d2 - d3, qc), quant_dc(d0 - d1 - d2 + d3, qc)};
-#endif
-            CapSink cap{0, 0, 0};
-            const int tc = cavlc_dc4(cap, L.ptabs, dq);
-            if (cap.n <= 128) {
-                mt[sl] = (uint16_t)(cap.n | (uint32_t)tc << 8);
-                lv[sl] = body_msb(cap.hi, cap.lo, cap.n);
-            } else {
-                mt[sl] = (uint16_t)((uint32_t)tc << 8 | M_OVF);       /* the levels in lv */
-#ifndef SCROLL_ROW_OLDREC
-                lv[sl] = make_uint4(((uint32_t)dq[0] & 0xffffu) | (uint32_t)dq[1] << 16,
-                                    ((uint32_t)dq[2] & 0xffffu) | (uint32_t)dq[3] << 16, 0u, 0u);
-#endif
-            }
-        }
-        if (t < SORT_KEYS) {                            /* class k = t: its base */
-            const uint32_t tot = L.kc[0][t];
+        /* class k's base: every wave scans the nine counts itself and reads
+         * back its own stores (the same words from every wave): no barrier
+         * between the levels and the sort's scatter */
+        {
+            const uint32_t tot = lane < SORT_KEYS ? L.kc[0][lane] : 0u;
             uint32_t kb = tot;
-#pragma unroll
-            for (int dd = 1; dd < 32; dd <<= 1) {
-                const uint32_t o = __shfl_up(kb, dd, 64);
-                if (lane >= dd) kb += o;
-            }
-            L.kc[1][t] = kb - tot;
+            kb += dpp_or0<0x111, 0xf>(kb);
+            kb += dpp_or0<0x112, 0xf>(kb);
+            kb += dpp_or0<0x114, 0xf>(kb);
+            kb += dpp_or0<0x118, 0xf>(kb);
+            if (lane < SORT_KEYS) L.kc[1][lane] = kb - tot;
+            wave_sync();
         }
-        __syncthreads();
         for (int task = t; task < ntask; task += T) {       /* the slot, chroma flagged in bit 15 */
             const int slot = row_slot(task, w);
 #ifdef SCROLL_ROW_OLDREC
@@ -2112,6 +2116,39 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
                           : (uint16_t)((uint32_t)tc << 8 | (uint32_t)t1 << 13 | M_OVF);
             if (ok) lv[slot] = body_msb(cap.hi, cap.lo, cap.n);
             else if (key) lv[slot] = lv_swz(lv[slot], key);     /* rare: the levels stay, in plain order */
+        }
+        /* chroma DC blocks, whole (nC = -1): their slots (k NPC + 16 + p of
+         * mt / lv) are no block task's, so nothing reads them before the
+         * token phase -- coded here, off the path to the sort, from the top
+         * of the last wave that does not poll down (the sort gave those
+         * threads the lightest bodies or none) */
+        const int dcT = nwv > 1 ? T - 64 : T;
+        for (int i = dcT - 1 - t; i >= 0 && i < 2 * w; i += dcT) {
+            const int k = i >> 1, p = i & 1, sl = k * NPC + 16 + p;
+            const uint4 q = lv[sl];
+#ifdef SCROLL_ROW_OLDREC
+            const int dq[4] = {(int)(int16_t)(q.x & 0xffffu), (int)(int16_t)(q.x >> 16),
+                               (int)(int16_t)(q.y & 0xffffu), (int)(int16_t)(q.y >> 16)};
+#else
+            /* the four DC coefficients of the plane's 4x4 blocks (raster) ->
+             * 2x2 Hadamard, quant (qbits + 1) */
+            const int d0 = (int)(int16_t)(q.x & 0xffffu), d1 = (int)(int16_t)(q.x >> 16);
+            const int d2 = (int)(int16_t)(q.y & 0xffffu), d3 = (int)(int16_t)(q.y >> 16);
+            const int dq[4] = {quant_dc(d0 + d1 + d2 + d3, qc), quant_dc(d0 - d1 + d2 - d3, qc),
+                               quant_dc(d0 + d1 - d2 - d3, qc), quant_dc(d0 - d1 - d2 + d3, qc)};
+#endif
+            CapSink cap{0, 0, 0};
+            const int tc = cavlc_dc4(cap, L.ptabs, dq);
+            if (cap.n <= 128) {
+                mt[sl] = (uint16_t)(cap.n | (uint32_t)tc << 8);
+                lv[sl] = body_msb(cap.hi, cap.lo, cap.n);
+            } else {
+                mt[sl] = (uint16_t)((uint32_t)tc << 8 | M_OVF);       /* the levels in lv */
+#ifndef SCROLL_ROW_OLDREC
+                lv[sl] = make_uint4(((uint32_t)dq[0] & 0xffffu) | (uint32_t)dq[1] << 16,
+                                    ((uint32_t)dq[2] & 0xffffu) | (uint32_t)dq[3] << 16, 0u, 0u);
+#endif
+            }
         }
     } else {
         /* general path: records of k_dyn_code_general */
@@ -2230,6 +2267,9 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         }
         lo[i] = (uint16_t)(len | nc1 << 11);
     };
+    /* phase 4's coded_block_pattern codes, entry `lane` in each lane (the
+     * load is in flight during the tokens) */
+    const uint32_t cbtab = TB.cbp_code[min(lane, 47)];
     for (int i = t; i < npc; i += T) {
         const int k = div_npc(i), pc = i - k * NPC;
         token(i, k, pc, L.pcd[pc]);
@@ -2246,41 +2286,68 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     };
 
     /* ---- 4: per MB cbp, code, piece offsets; the row's MB offsets ------- */
-    for (int k = t; k < w; k += T) {
-        const uint16_t *mk = mt + k * NPC;
-        int cbp_l = 0;
-#pragma unroll
-        for (int pc = 0; pc < 16; ++pc)
-            if (tc_of(mk[pc])) cbp_l |= 1 << (2 * (pc >> 3) + ((pc & 3) >> 1));
-        bool ac = false;
-#pragma unroll
-        for (int pc = 18; pc < NPC; ++pc) ac |= tc_of(mk[pc]) != 0;
-        const bool dc = (tc_of(mk[16]) | tc_of(mk[17])) != 0;
-        const int cbp_c = ac ? 2 : (dc ? 1 : 0);
-        const int cbp = cbp_l | cbp_c << 4;
-        const int code = TB.cbp_code[cbp];
-        CountSink hs{head_bits(row, R.x0 + k)};
-        put_ue(hs, (uint32_t)code);
-        if (cbp) put_se(hs, 0);                         /* mb_qp_delta */
-        uint32_t off = hs.n;
-        const uint16_t *lk = lo + k * NPC;
-        uint16_t *ok = off16 + k * NPC;
-#pragma unroll
-        for (int blk = 0; blk < 16; ++blk) {            /* luma4x4BlkIdx order */
-            const int rr = blk_raster(blk);
-            const bool pres = (cbp_l >> (blk >> 2)) & 1;
-            ok[rr] = pres ? (uint16_t)off : (uint16_t)0xffffu;
-            off += pres ? (lk[rr] & LO_LEN) : 0u;
+    /* Eight lanes per MB, each with one run of the MB's pieces in coding
+     * order: lanes 0-3 the four 4x4 blocks of luma 8x8 block 0-3, lane 4 the
+     * two chroma DC blocks, lanes 5 / 6 the Cb / Cr AC blocks, lane 7 the
+     * MB's total.  A run is present or absent as a whole (one cbp bit, or
+     * the chroma cbp), so one ballot of "a TotalCoeff != 0 in my run" is the
+     * MB's cbp, and a prefix sum of the runs' lengths over the eight lanes
+     * gives each run's offset.  T / 8 MBs a pass (a config-3 row in one); a
+     * wave without an MB left is done.  lo / mt are phase 3's, behind its
+     * barrier; off16 overlays the CAVLC phase's order (last read before the
+     * barrier that ends phases 1-2) and mbits overlays ta (last read in
+     * phase 3). */
+    {
+        const int j = t & 7, G = T >> 3;
+        const bool lum = j < 4, four = j != 4;
+        const int pb = lum ? 8 * (j >> 1) + 2 * (j & 1) : (j == 4 ? 16 : (j == 5 ? 18 : 22));
+        const int d2 = lum ? 4 : 2, d3 = d2 + 1;        /* the run: pb, pb + 1, pb + d2, pb + d3 */
+        for (int k0 = wv0 >> 3; k0 < w; k0 += G) {      /* the wave's first MB of the pass */
+            const int k = k0 + (lane >> 3);
+            const bool live = k < w && j < 7;
+            const int i0 = (int)__umul24((uint32_t)k, (uint32_t)NPC) + pb;
+            uint32_t mm = 0u, l0 = 0u, l1 = 0u, l2 = 0u, l3 = 0u;
+            if (live) {
+                mm = (uint32_t)mt[i0] | mt[i0 + 1];
+                l0 = lo[i0] & LO_LEN;
+                l1 = lo[i0 + 1] & LO_LEN;
+                if (four) {
+                    mm |= (uint32_t)mt[i0 + d2] | mt[i0 + d3];
+                    l2 = lo[i0 + d2] & LO_LEN;
+                    l3 = lo[i0 + d3] & LO_LEN;
+                }
+            }
+            const uint64_t nzw = __builtin_amdgcn_ballot_w64((mm & 0x1f00u) != 0u);     /* tc_of */
+            const uint32_t m = (uint32_t)(nzw >> (lane & 56)) & 0x7fu;
+            const uint32_t cbp_l = m & 15u, cbp_c = (m & 0x60u) ? 2u : (m >> 4);
+            const uint32_t cbp = cbp_l | cbp_c << 4;
+            const uint32_t code = (uint32_t)__shfl((int)cbtab, (int)cbp, 64);
+            const bool pres = lum ? (m >> j) & 1u : (j == 4 ? cbp_c >= 1u : cbp_c == 2u);
+            const uint32_t tot = pres ? l0 + l1 + l2 + l3 : 0u;
+            uint32_t incl = tot, u;
+            u = dpp_or0<0x111, 0xf>(incl);
+            incl += j >= 1 ? u : 0u;
+            u = dpp_or0<0x112, 0xf>(incl);
+            incl += j >= 2 ? u : 0u;
+            u = dpp_or0<0x114, 0xf>(incl);
+            incl += j >= 4 ? u : 0u;
+            /* the MB's head, ue(code) and mb_qp_delta se(0) */
+            const uint32_t hb = head_bits(row, R.x0 + min(k, w - 1)) + ue_bits(code) + (cbp ? 1u : 0u);
+            const uint32_t o0 = hb + incl - tot, no = pres ? 0u : 0xffffu;     /* absent: 0xffff */
+            if (live) {
+                off16[i0] = (uint16_t)(o0 | no);
+                off16[i0 + 1] = (uint16_t)((o0 + l0) | no);
+                if (four) {
+                    off16[i0 + d2] = (uint16_t)((o0 + l0 + l1) | no);
+                    off16[i0 + d3] = (uint16_t)((o0 + l0 + l1 + l2) | no);
+                }
+            }
+            if (j == 7 && k < w) {
+                mbits[k] = hb + incl;
+                cbpa[k] = (uint8_t)cbp;
+                codea[k] = (uint8_t)code;
+            }
         }
-#pragma unroll
-        for (int k2 = 16; k2 < NPC; ++k2) {             /* Cb DC, Cr DC, Cb AC 0-3, Cr AC 0-3 */
-            const bool pres = k2 < 18 ? cbp_c >= 1 : cbp_c == 2;
-            ok[k2] = pres ? (uint16_t)off : (uint16_t)0xffffu;
-            off += pres ? (lk[k2] & LO_LEN) : 0u;
-        }
-        mbits[k] = off;
-        cbpa[k] = (uint8_t)cbp;
-        codea[k] = (uint8_t)code;
     }
     /* the bit offset of column col in the row: a static column's head (+ its
      * coded_block_pattern '1') is the row's first / middle / last class, so
@@ -2295,20 +2362,32 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         if (col < x1) return moff[col - R.x0];
         return moff[w] + (uint32_t)(col - x1) * h1 + (col == mbw && x1 <= mbw - 1 ? h2 - h1 : 0u);
     };
-    __syncthreads();
+    __syncthreads();                                    /* mbits, cbpa, codea, off16 */
     const int gi = nA + r;
-    if (wave == 0) {
-        uint32_t carry = R.x0 == 0 ? 0u : h0 + (uint32_t)(R.x0 - 1) * h1;
-        for (int k0 = 0; k0 < w; k0 += 64) {
-            const int k = k0 + lane;
-            const uint32_t len = k < w ? mbits[k] : 0u;
-            const uint32_t incl = wave_incl_sum(len, lane);
-            if (k < w) moff[k] = carry + incl - len;
-            carry += __shfl(incl, 63, 64);
+    const uint32_t mb0 = R.x0 == 0 ? 0u : h0 + (uint32_t)(R.x0 - 1) * h1;
+    if (w <= 64) {
+        /* one scan pass: every wave makes the whole of moff itself and reads
+         * back only its own stores (the other waves store the same words),
+         * so the waves need no second barrier */
+        const uint32_t len = lane < w ? mbits[lane] : 0u;
+        const uint32_t incl = wave_incl_sum_dpp(len);
+        if (lane < w) moff[lane] = mb0 + incl - len;
+        if (lane == w - 1) moff[w] = mb0 + incl;
+        wave_sync();
+    } else {
+        if (wave == 0) {
+            uint32_t carry = mb0;
+            for (int k0 = 0; k0 < w; k0 += 64) {
+                const int k = k0 + lane;
+                const uint32_t len = k < w ? mbits[k] : 0u;
+                const uint32_t incl = wave_incl_sum_dpp(len);
+                if (k < w) moff[k] = carry + incl - len;
+                carry += __shfl(incl, 63, 64);
+            }
+            if (lane == 0) moff[w] = carry;
         }
-        if (lane == 0) moff[w] = carry;
+        __syncthreads();
     }
-    __syncthreads();
     if (stp) stp[4] = __builtin_amdgcn_s_memrealtime();
     ROW_CUT(4);
     const uint32_t bits = colpos(mbw);
