@@ -276,6 +276,43 @@ void sim_fwd_quant(const int *res, int *lv)
 
 int sim_quant_dc(int w) { return dyn::quant_dc(w, Q26); }
 
+/* the quantiser at a QP known at run time, as the kernels take it (qparams_rt) */
+int sim_quant_qp(int w, int pos, int qp) { return dyn::quant(w, pos, dyn::qparams_rt(qp)); }
+int sim_quant_dc_qp(int w, int qp) { return dyn::quant_dc(w, dyn::qparams_rt(qp)); }
+
+/* quant / quant_dc through qparams_rt against a reference quantiser
+ * ref(w, qp, pos, dc_chroma) for every QP 0..51, every raster position and
+ * every |w| up to the position class's largest transform output (16 x 255 at
+ * (even, even), 36 x 255 at (odd, odd), 24 x 255 mixed; 64 x 255 for the
+ * chroma DC sum), both signs; qparams_rt must also equal the compile-time
+ * qparams.  Returns the number of comparisons, or -1 with the first failing
+ * (qp, pos, w, dc, got, want) in bad[6]. */
+typedef int (*sim_quant_ref_fn)(int w, int qp, int pos, int dc_chroma);
+long sim_quant_sweep(sim_quant_ref_fn ref, int *bad)
+{
+    long n = 0;
+    for (int qp = 0; qp <= 51; ++qp) {
+        const QParams q = dyn::qparams_rt(qp), qc = dyn::qparams(qp);
+        if (std::memcmp(&q, &qc, sizeof q) != 0) {
+            bad[0] = qp, bad[1] = -1, bad[2] = bad[3] = bad[4] = bad[5] = 0;
+            return -1;
+        }
+        for (int pos = 0; pos <= 16; ++pos) {
+            const int dc = pos == 16, i = pos >> 2, j = pos & 3;
+            const int wmax = dc ? 16320 : (((i | j) & 1) == 0 ? 4080 : (((i & j) & 1) ? 9180 : 6120));
+            for (int w = -wmax; w <= wmax; ++w, ++n) {
+                const int got = dc ? dyn::quant_dc(w, q) : dyn::quant(w, pos, q);
+                const int want = ref(w, qp, dc ? 0 : pos, dc);
+                if (got != want) {
+                    bad[0] = qp, bad[1] = pos, bad[2] = w, bad[3] = dc, bad[4] = got, bad[5] = want;
+                    return -1;
+                }
+            }
+        }
+    }
+    return n;
+}
+
 int sim_ep_count(const uint8_t *b, int n)
 {
     int prev = -1, c = 0;

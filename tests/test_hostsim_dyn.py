@@ -166,6 +166,59 @@ def test_transform_quant_vs_oracle(hostsim, oracle):
         assert hostsim.sim_quant_dc(v) == oracle.or_quant(v, 26, 0, 1)
 
 
+# the largest transform output per raster position: 16 x 255 at (even, even),
+# 36 x 255 at (odd, odd), 24 x 255 at the mixed positions; 64 x 255 for the
+# 2x2 chroma DC sum
+def _wmax(pos):
+    i, j = divmod(pos, 4)
+    return 4080 if (i % 2 == 0 and j % 2 == 0) else (9180 if (i % 2 and j % 2) else 6120)
+
+
+WMAX_DC = 16320
+
+
+def test_quant_every_qp_vs_oracle(hostsim, oracle):
+    """quant / quant_dc through qparams_rt (the kernels' way to a run-time QP)
+    against or_quant: every QP 0..51, every position, every |W| up to the
+    position class's maximum and both signs -- exhaustive, the clamp to 2063
+    included.  The loop runs in the CPU build and calls or_quant itself."""
+    ref = ctypes.cast(oracle.or_quant, ctypes.c_void_p)
+    bad = (ctypes.c_int * 6)()
+    hostsim.sim_quant_sweep.restype = ctypes.c_long
+    hostsim.sim_quant_sweep.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+    n = hostsim.sim_quant_sweep(ref, bad)
+    assert n >= 0, "qp %d pos %d w %d dc %d: %d, or_quant %d" % tuple(bad)
+    want = 52 * (sum(2 * _wmax(p) + 1 for p in range(16)) + 2 * WMAX_DC + 1)
+    assert n == want, (n, want)
+    print(f"quantiser: {n} (QP, position, W) values equal or_quant")
+    # the single entry points agree with the sweep's functions at a few spots
+    for qp, pos, w in [(0, 0, 4080), (22, 5, -9180), (51, 1, 6120), (21, 0, -4080)]:
+        assert hostsim.sim_quant_qp(w, pos, qp) == oracle.or_quant(w, qp, pos, 0)
+    for qp, w in [(0, 16320), (0, -16320), (39, 16320)]:
+        assert hostsim.sim_quant_dc_qp(w, qp) == oracle.or_quant(w, qp, 0, 1)
+
+
+def test_qp_min_and_clamp_from_oracle(oracle):
+    """QP_MIN = 22 and LEVEL_MAX = 2063 (dyn_device.h) from or_quant alone:
+    the largest luma / chroma AC level is exactly 127 at QP 22 (k_dyn_row's
+    int8 records hold it) and exceeds 127 at QP 21; the largest chroma DC
+    level at QP 0 is clamped to exactly 2063, both signs"""
+    def largest(qp):
+        return max(oracle.or_quant(_wmax(p), qp, p, 0) for p in range(16))
+
+    assert largest(22) == 127
+    assert min(oracle.or_quant(-_wmax(p), 22, p, 0) for p in range(16)) == -127
+    assert largest(21) > 127
+    assert all(largest(qp) <= 127 for qp in range(22, 52))
+    assert all(largest(qp) > 127 for qp in range(0, 22))
+    assert oracle.or_quant(WMAX_DC, 0, 0, 1) == 2063
+    assert oracle.or_quant(-WMAX_DC, 0, 0, 1) == -2063
+    unclamped = (WMAX_DC * 13107 + 2 * ((1 << 15) // 6)) >> 16      # 8.5-style forward DC at QP 0
+    assert unclamped > 2063
+    print(f"largest level: {largest(22)} at QP 22, {largest(21)} at QP 21; chroma DC at QP 0 "
+          f"{unclamped} clamped to 2063")
+
+
 def _ep_automaton(b):
     zeros, n = 0, 0
     for v in b:
