@@ -1166,12 +1166,10 @@ constexpr LvTab make_lvt()
  *     from them;
  *   - the level loop as in cavlc_body;
  *   - total_zeros + run_before as one field from the entry.
- * Same bits, TotalCoeff, TrailingOnes and ok as cavlc_body<CAP, true>.
- * bx: level i is byte i ^ bx of lb (k_dyn_row's records with their dwords
- * swizzled per slot, so lanes on consecutive slots read different banks) */
+ * Same bits, TotalCoeff, TrailingOnes and ok as cavlc_body<CAP, true>. */
 template <class CAP>
 __device__ __host__ inline int cavlc_body_t(CAP &cap, const int8_t *lb, uint32_t nz, uint32_t tzrb, int &t1o,
-                                            bool &ok, const uint32_t *lvt, uint32_t bx = 0)
+                                            bool &ok, const uint32_t *lvt)
 {
     const int tc = __builtin_popcount(nz);
     /* g: the mask shifted up one with a guard bit 0 -- clz(g) <= 31, and
@@ -1183,7 +1181,7 @@ __device__ __host__ inline int cavlc_body_t(CAP &cap, const int8_t *lb, uint32_t
     const uint32_t g2 = g1 & ~((0x80000000u >> c1) & ~1u);
     const int c2 = __builtin_clz(g2);
     const uint32_t g3 = g2 & ~((0x80000000u >> c2) & ~1u);
-    const int v0 = lb[(30 - c0) ^ (int)bx], v1 = lb[(30 - c1) ^ (int)bx], v2 = lb[(30 - c2) ^ (int)bx];
+    const int v0 = lb[30 - c0], v1 = lb[30 - c1], v2 = lb[30 - c2];
     /* a level is a trailing one iff it exists (not the guard) and is +-1 */
     const bool o0 = c0 < 31 && v0 * v0 == 1, o1 = o0 && c1 < 31 && v1 * v1 == 1;
     const bool o2 = o1 && c2 < 31 && v2 * v2 == 1;
@@ -1224,7 +1222,6 @@ __device__ __host__ inline int cavlc_body_t(CAP &cap, const int8_t *lb, uint32_t
         const int s1 = sl == 0 ? 1 : sl;
         return fv | fl << 13 | (uint32_t)(s1 + ((a > (3 << (s1 - 1)) && s1 < 6) ? 1 : 0)) << 18;
     };
-#ifndef SCROLL_CAVLC_NOPF
     /* round 6: the loop holds the table path only (levels clamped into the
      * table, a lane whose block has a level past LVT_V flagged), so the rare
      * arithmetic form costs no exec-mask branch per level; a flagged lane
@@ -1238,12 +1235,12 @@ __device__ __host__ inline int cavlc_body_t(CAP &cap, const int8_t *lb, uint32_t
     const CAP cap0 = cap;
     bool big = false;
     int pn = top_bit(m);
-    int vn = (int)lb[pn ^ (int)bx];
+    int vn = (int)lb[pn];
     for (int k = t1; k < tc; ++k) {                        /* levels below the trailing ones */
         const int v = vn;
         m &= ~(1u << pn);
         pn = top_bit(m);
-        vn = (int)lb[pn ^ (int)bx];
+        vn = (int)lb[pn];
         const int vc = v < -LVT_V ? -LVT_V : (v > LVT_V ? LVT_V : v);
         big |= vc != v;
         const uint32_t e = lvt[cls * LVT_W + vc + LVT_V + 1];
@@ -1259,20 +1256,11 @@ __device__ __host__ inline int cavlc_body_t(CAP &cap, const int8_t *lb, uint32_t
         for (int k = t1; k < tc; ++k) {
             const int p = top_bit(m);
             m &= ~(1u << p);
-            const uint32_t e = level_code((int)lb[p ^ (int)bx], cls);
+            const uint32_t e = level_code((int)lb[p], cls);
             push(acc, an, e & 0x1fffu, (e >> 13) & 31u, cap);
             cls = (int)(e >> 18);
         }
     }
-#else
-    for (int k = t1; k < tc; ++k) {
-        const int p = top_bit(m);
-        m &= ~(1u << p);
-        const uint32_t e = level_code((int)lb[p ^ (int)bx], cls);
-        push(acc, an, e & 0x1fffu, (e >> 13) & 31u, cap);
-        cls = (int)(e >> 18);
-    }
-#endif
     /* total_zeros + run_before: the entry's code, len = 31 - ctz */
     const uint32_t tzl = 31u - (uint32_t)__builtin_ctz(tzrb);
     push(acc, an, (tzrb >> 1) >> (31u - tzl), tzl, cap);

@@ -35,7 +35,6 @@
 #include "dyn_device.h"
 #include "dyn_engine.h"
 #include "nal_ctx.h"
-#include "row_mfma.h"
 #include "stage_util.h"
 
 using namespace scroll;
@@ -910,10 +909,6 @@ constexpr int GW = 64;
 #endif
 constexpr int GBUF_WORDS = SCROLL_GBUF_WORDS;   /* 8 Kbit per pass */
 
-#ifndef SCROLL_STATIC_WORDS
-#define SCROLL_STATIC_WORDS 1       /* static rows word by word from the head patterns (0: MB by MB) */
-#endif
-
 struct StaticFixed {
     uint32_t ncand;
     uint32_t buf[GBUF_WORDS];
@@ -1030,13 +1025,13 @@ __global__ __launch_bounds__(GW) void k_dyn_static(const DevStream *__restrict__
         for (uint32_t i = (uint32_t)t; i < n; i += GW) L.buf[i] = 0u;
         wave_sync();
         const LdsOrWin win{L.buf, p0, n};
-        if (!(SCROLL_STATIC_WORDS && !head_over) && first && t == 0 && p0 * 32u < F) {   /* slice header, h264_writer.c:549-553 */
+        if (head_over && first && t == 0 && p0 * 32u < F) {   /* slice header, h264_writer.c:549-553 */
             WSink hs{win, 0, 0, 0};
             hs.start(0);
             emit_slice_header(hs, c);
             hs.finish();
         }
-        if (SCROLL_STATIC_WORDS && !head_over) {
+        if (!head_over) {
             /* word by word: a static row is its first column's head, mbw - 2
              * copies of the middle class's, the last column's (each with the
              * cbp '1': the patterns); a lane builds whole words of the window
@@ -1175,30 +1170,13 @@ __device__ inline void put_piece(uint32_t *buf, uint32_t p0, uint32_t n, uint32_
 }
 
 /* put_piece for a row written in one pass (the window is the row's words
- * from 0, with ROW_PAD spare words after it): the first SCROLL_PUT_FIRST
- * words ORed whatever the piece's length (zero words past its end change
- * nothing), the rest only for pieces that reach them -- no window tests.
- * Round 6: 1 instead of 3 -- a zero OR into the word the next lane's piece
- * starts in is a same-address LDS conflict (k_dyn_row's conflicts 112 ->
- * 91 M per config-3 launch, its time equal within noise) */
+ * from 0, with ROW_PAD spare words after it): word 0 ORed always, the rest
+ * only for pieces that reach them (nw) -- no window tests.  ORing words 1
+ * and 2 always as well put zero ORs into the word the next lane's piece
+ * starts in, a same-address LDS conflict (k_dyn_row's conflicts 112 -> 91 M
+ * per config-3 launch without them, its time equal within noise) */
 constexpr uint32_t ROW_PAD = 4;
 
-/* SCROLL_LV_SWZ=1 (measured, not kept): k_dyn_row's level records between
- * the sort and the CAVLC bodies with dword d of the record in slot s at
- * d ^ lv_key(s) (an involution), swizzled in the sort's pass -- LDS bank
- * conflicts 91 -> 68 M per config-3 launch, but k_dyn_row 1.206 -> 1.232 ms
- * (the extra record read / permute / write per block costs more than the
- * conflicts did; profiles/r06j_lds_swizzle_p720dyn.txt) */
-#ifndef SCROLL_LV_SWZ
-#define SCROLL_LV_SWZ 0
-#endif
-__device__ inline uint32_t lv_key(int slot) { return ((uint32_t)slot >> 4) & 3u; }
-__device__ inline uint4 lv_swz(uint4 v, uint32_t key)
-{
-    if (key & 1u) v = make_uint4(v.y, v.x, v.w, v.z);
-    if (key & 2u) v = make_uint4(v.z, v.w, v.x, v.y);
-    return v;
-}
 __device__ inline void put_piece1(uint32_t *buf, uint32_t pos, uint32_t tv, uint32_t tl, uint4 b, uint32_t bl)
 {
     const uint32_t tw = tv & low_mask((int)tl);
@@ -1207,12 +1185,9 @@ __device__ inline void put_piece1(uint32_t *buf, uint32_t pos, uint32_t tv, uint
     const uint32_t c4 = __builtin_amdgcn_alignbit(b.w, 0u, tl);
     const uint32_t sh = pos & 31u, nw = (sh + tl + bl + 31u) >> 5;
     uint32_t *d = buf + (pos >> 5);
-#ifndef SCROLL_PUT_FIRST
-#define SCROLL_PUT_FIRST 1       /* words ORed whatever the length (round 6: 3 -> 1, fewer same-address ORs) */
-#endif
     atomicOr(d, c0 >> sh);
-    if (SCROLL_PUT_FIRST >= 2 || nw > 1u) atomicOr(d + 1, __builtin_amdgcn_alignbit(c0, c1, sh));
-    if (SCROLL_PUT_FIRST >= 3 || nw > 2u) atomicOr(d + 2, __builtin_amdgcn_alignbit(c1, c2, sh));
+    if (nw > 1u) atomicOr(d + 1, __builtin_amdgcn_alignbit(c0, c1, sh));
+    if (nw > 2u) atomicOr(d + 2, __builtin_amdgcn_alignbit(c1, c2, sh));
     if (nw > 3u) {
         atomicOr(d + 3, __builtin_amdgcn_alignbit(c2, c3, sh));
         if (nw > 4u) {
@@ -1407,7 +1382,7 @@ struct FetchOff {
 
 /* luma task v (MB k = v / 16, raster block v % 16) of rect row ry; rt = the
  * row's 16 luma prediction rows (LDS, or k_dyn_rows' table in global memory) */
-[[maybe_unused]] __device__ inline void fetch_luma(FetchOff &o, int v, int ry, const DynGeom &g, const uint32_t *rt)
+__device__ inline void fetch_luma(FetchOff &o, int v, int ry, const DynGeom &g, const uint32_t *rt)
 {
     const int k = v >> 4, r = v & 15, bx = r & 3, by = r >> 2;
     o.s = (uint32_t)((16 * ry + 4 * by) * (16 * g.w) + 16 * k + 4 * bx);
@@ -1419,7 +1394,7 @@ struct FetchOff {
 
 /* chroma AC task e (MB e / 8, plane (e / 4) % 2, raster block e % 4); ru /
  * rd = the row's 8 upper / lower bilinear rows */
-[[maybe_unused]] __device__ inline void fetch_chroma(FetchOff &o, int e, int ry, const DynGeom &g, uint32_t csz, const uint32_t *ru,
+__device__ inline void fetch_chroma(FetchOff &o, int e, int ry, const DynGeom &g, uint32_t csz, const uint32_t *ru,
                                     const uint32_t *rd)
 {
     const int ndt = g.w * g.h, k = e >> 3, p = (e >> 2) & 1, r = e & 3, bx = r & 1, by = r >> 1;
@@ -1434,33 +1409,12 @@ struct FetchOff {
  * past the row's tasks load too: their offsets stay inside the frame's
  * source / the reference pair or read 0 past the descriptor (raw buffer
  * range check), and their results are never stored.  Chroma always loads
- * its lower row (used only with a fraction): no wait for the fraction */
-[[maybe_unused]] __device__ inline void fetch_pass(const FetchOff &o, bool luma, uint32_t adv, uint32_t stride,
-                                  __amdgpu_buffer_rsrc_t fs, __amdgpu_buffer_rsrc_t rb, BlkPix &px)
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        px.a[i] = __builtin_amdgcn_raw_buffer_load_b32(fs, o.s, adv + (uint32_t)i * stride, 0);
-        px.b[i] = __builtin_amdgcn_raw_buffer_load_b32(rb, o.b[i], adv, 0);
-    }
-    px.c = luma ? 0u : __builtin_amdgcn_raw_buffer_load_b32(rb, o.c, adv, 0);
-}
-/* the same with the ninth load for luma too (o.c = o.b[3]; its value unused):
- * every pass issues nine loads (k_dyn_row's counted waits) */
-[[maybe_unused]] __device__ inline void fetch_pass9(const FetchOff &o, uint32_t adv, uint32_t stride, __amdgpu_buffer_rsrc_t fs,
+ * its lower row (used only with a fraction): no wait for the fraction.  Luma
+ * issues the ninth load too (o.c = o.b[3]; its value unused): every pass is
+ * nine loads (k_dyn_row's counted waits) */
+__device__ inline void fetch_pass9(const FetchOff &o, uint32_t adv, uint32_t stride, __amdgpu_buffer_rsrc_t fs,
                                    __amdgpu_buffer_rsrc_t rb, BlkPix &px)
 {
-#ifdef SCROLL_ABL_NOLOAD
-    /* profiling variant only: no pixel loads (values from the offsets), the
-     * ceiling of any change to how the pixels are fetched */
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        px.a[i] = (o.s + adv + (uint32_t)i * stride) * 0x9e3779b1u;
-        px.b[i] = (o.b[i] + adv) * 0x85ebca6bu;
-    }
-    px.c = o.c + adv;
-    return;
-#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         px.a[i] = __builtin_amdgcn_raw_buffer_load_b32(fs, o.s, adv + (uint32_t)i * stride, 0);
@@ -1468,60 +1422,6 @@ struct FetchOff {
     }
     px.c = __builtin_amdgcn_raw_buffer_load_b32(rb, o.c, adv, 0);
 }
-
-/* round 6, an opt-in build (-DSCROLL_ROW_MFMA; the product path is the
- * vector form: the north star prescribes no MFMA for this integer path, and
- * the matrix-core form measured only 2.5 % faster): the
- * matrix-core levels (row_mfma.h).  A wave's pass = 64 tasks
- * = 4 tiles; lane (g = lane / 16, n = lane % 16) loads 16 bytes of one
- * source row, of its prediction row and (chroma) of the lower bilinear row:
- *   luma:   n = (MB m = n / 4 of the wave's four, block row n % 4), pixel
- *           row g of the block row; tile j = block column j;
- *   chroma: n = (plane n / 8, block row (n / 4) % 2, MB pair n % 4), pixel
- *           row g; tile j = (MB j / 2 of the pair, block column j % 2).
- * The offsets advance by T bytes per pass as FetchOff's (16 or 8 bytes per
- * MB, T / 16 or T / 8 MBs per pass) */
-struct MFetch {
-    uint32_t s, p, q;           /* source row; prediction row; its lower bilinear row (chroma) */
-    int pb;
-};
-struct MPix {
-    uint4 s, p, q;
-};
-[[maybe_unused]] __device__ inline void mfetch_luma(MFetch &o, int v0, int ry, const DynGeom &g, const uint32_t *rt, int lane)
-{
-    const int gq = lane >> 4, n = lane & 15, k = (v0 >> 4) + (n >> 2), y = 4 * (n & 3) + gq;
-    o.s = (uint32_t)((16 * ry + y) * (16 * g.w) + 16 * k);
-    o.p = (uint32_t)(16 * (g.x0 + k)) + rt[y];
-    o.q = o.p;
-}
-[[maybe_unused]] __device__ inline void mfetch_chroma(MFetch &o, int e0, int ry, const DynGeom &g, uint32_t csz, const uint32_t *ru,
-                                     const uint32_t *rd, int lane)
-{
-    const int ndt = g.w * g.h, gq = lane >> 4, n = lane & 15, p = n >> 3, by = (n >> 2) & 1;
-    const int k = (e0 >> 3) + 2 * (n & 3), y = 4 * by + gq;
-    o.s = (uint32_t)(256 * ndt + (p ? 64 * ndt : 0) + (8 * ry + y) * (8 * g.w) + 8 * k);
-    const uint32_t co = (uint32_t)p * csz + (uint32_t)(8 * (g.x0 + k));
-    o.p = co + (ru[y] & ROW_OFF);
-    o.q = co + ((gq < 3 ? ru[y + 1] : rd[y]) & ROW_OFF);
-}
-[[maybe_unused]] __device__ inline void mfetch_pass(const MFetch &o, bool chroma, uint32_t adv, __amdgpu_buffer_rsrc_t fs,
-                                   __amdgpu_buffer_rsrc_t rb, MPix &px)
-{
-    const auto a = __builtin_amdgcn_raw_buffer_load_b128(fs, o.s, adv, 0);
-    const auto b = __builtin_amdgcn_raw_buffer_load_b128(rb, o.p, adv, 0);
-    px.s = make_uint4(a[0], a[1], a[2], a[3]);
-    px.p = make_uint4(b[0], b[1], b[2], b[3]);
-    if (chroma) {
-        const auto c = __builtin_amdgcn_raw_buffer_load_b128(rb, o.q, adv, 0);
-        px.q = make_uint4(c[0], c[1], c[2], c[3]);
-    } else {
-        px.q = px.p;            /* every field written: the sets stay in registers */
-    }
-}
-#ifdef SCROLL_ROW_MFMA
-__constant__ KMat g_kmat = make_kmat();
-#endif
 
 /* ((8 - f) b + f c + 4) >> 3 for the four bytes of b, c: even and odd bytes
  * as two 16-bit halves each (at most 2,044: no carry between halves), two
@@ -1551,15 +1451,6 @@ __device__ inline int row_slot(int task, int w)
     const int k = l ? task >> 4 : jj >> 3, pc = l ? task & 15 : 18 + (jj & 7);
     return (int)__umul24((uint32_t)k, (uint32_t)NPC) + pc;   /* no quarter-rate multiply */
 }
-
-/* profiling variants only (tools/build_variant.sh, -DSCROLL_ABL_STOP=n):
- * the workgroup stops after phase n, for per-phase time and VALU counts */
-#ifdef SCROLL_ABL_STOP
-#define ROW_CUT(n) \
-    if ((n) == SCROLL_ABL_STOP) return
-#else
-#define ROW_CUT(n) (void)0
-#endif
 
 /* grid (h, frames, streams), row_threads(w) threads, row_lds_bytes dynamic LDS.
  * GEN: the instantiation for the NALs k_dyn_rows flagged for the general
@@ -1627,26 +1518,6 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
      * LDS copy of the table (a frame this instantiation does not code reads
      * a table k_dyn_rows did not write: offsets into the descriptors' ranges
      * or past them, which read 0; nothing is stored) */
-#ifdef SCROLL_ROW_MFMA
-    MFetch mo;
-    mo.pb = -1;
-    bool mo_chroma = false;
-    MPix mx;
-    if (!general) {
-        const uint32_t *rtg = rows + nb * (size_t)(32 * g.h);
-        const int k0 = kind_of(0);
-        if (k0 == 0) {
-            mfetch_luma(mo, wv0, r, g, rtg + 16 * r, lane);
-            mo.pb = 0;
-            mfetch_pass(mo, false, 0u, fs, rb, mx);
-        } else if (k0 == 1) {
-            mfetch_chroma(mo, wv0 - L0, r, g, csz, rtg + 16 * g.h + 8 * r, rtg + 24 * g.h + 8 * r, lane);
-            mo.pb = 0;
-            mo_chroma = true;
-            mfetch_pass(mo, true, 0u, fs, rb, mx);
-        }
-    }
-#else
     FetchOff fo;
     fo.pb = -1;
     bool fo_chroma = false;
@@ -1665,7 +1536,6 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             fetch_pass9(fo, 0u, (uint32_t)(8 * w), fs, rb, nx);
         }
     }
-#endif
     const DynFrame df = dfr[nb];
     if (df.nal < 0 || ((df.err & DF_GENERAL) != 0) != GEN) return;
 
@@ -1704,7 +1574,6 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
 
     /* ---- 1-2: records (levels -> CAVLC bodies) into LDS ---------------- */
     __syncthreads();                                    /* the row table (rt) */
-    ROW_CUT(0);
     if (!general) {
         static_assert(ROW_MAXT % 64 == 0, "row_threads gives whole waves: the per-pass step T is a multiple of 64");
         /* the row's chroma fraction, the same for all its rows (one region,
@@ -1714,82 +1583,6 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         /* the stream's rect QP (QP_MIN and up here: int8 levels) */
         const int qpy = __builtin_amdgcn_readfirstlane(S->dyn_qp);
         const QParams ql = g_qptab.q[qpy].l, qc = g_qptab.q[qpy].c;
-#if defined(SCROLL_ROW_LVOLD) && !defined(SCROLL_ROW_MFMA)
-        auto issue = [&](int q, BlkPix &px) {
-            const int kd = kind_of(q);
-            if (kd == 2) return;
-            if (kd == 0 && fo.pb < 0) {
-                fetch_luma(fo, q * T + t, r, g, L.rt);
-                fo.pb = q;
-            } else if (kd == 1 && !fo_chroma) {
-                fetch_chroma(fo, q * T + t - L0, r, g, csz, L.rt + 16, L.rt + 24);
-                fo.pb = q;
-                fo_chroma = true;
-            }
-            fetch_pass(fo, kd == 0, (uint32_t)((q - fo.pb) * T), (uint32_t)(kd == 0 ? 16 * w : 8 * w), fs, rb, px);
-        };
-        /* counting sort on TotalCoeff class: a task's rank in its class from
-         * an LDS atomic (the order inside a class does not matter), kept in
-         * lo[] (phase 3's) until the class bases are known */
-        auto compute = [&](int q, const BlkPix &px) {
-            const int kd = kind_of(q);
-            if (kd == 2) return;
-            const int v = q * T + t;
-            uint32_t pk[4];
-            int w0 = 0;
-            if (kd == 0) {
-                levels_pk<true>(px.a, px.b, pk, w0, ql);
-            } else {
-                uint32_t pr[4];
-                if (frc == 4u) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) pr[i] = __builtin_amdgcn_lerp(px.b[i], i < 3 ? px.b[i + 1] : px.c, 0x01010101u);
-                } else if (frc == 0u) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) pr[i] = px.b[i];
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) pr[i] = bilin4(px.b[i], i < 3 ? px.b[i + 1] : px.c, frc);
-                }
-                levels_pk<false>(px.a, pr, pk, w0, qc);
-            }
-            const int e = v - L0;                           /* chroma task index */
-            const bool ok = kd == 0 ? v < nl : e < 8 * w;
-            if (ok) {
-                const int n = nz_bytes(pk[0]) + nz_bytes(pk[1]) + nz_bytes(pk[2]) + nz_bytes(pk[3]);
-                const int slot = kd == 0 ? (int)__umul24((uint32_t)(v >> 4), (uint32_t)NPC) + (v & 15)
-                                         : (int)__umul24((uint32_t)(e >> 3), (uint32_t)NPC) + 18 + (e & 7);
-                lv[slot] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-                mt[slot] = (uint16_t)((uint32_t)min(n, 16) << 8);
-                lo[slot] = (uint16_t)atomicAdd(&L.kc[0][SORT_KEYS - 1 - min(n, SORT_KEYS - 1)], 1u);
-            }
-            /* chroma DC: the quad's four DC coefficients -> 2x2 Hadamard,
-             * quant -> levels as int16 in the DC slot (coded after the
-             * barrier that publishes the CAVLC tables); quads are lane-aligned
-             * (L0 and T are multiples of 64) */
-            if (kd == 1) {
-                const int qb = lane & ~3;
-                const int d0 = __shfl(w0, qb, 64), d1 = __shfl(w0, qb + 1, 64);
-                const int d2 = __shfl(w0, qb + 2, 64), d3 = __shfl(w0, qb + 3, 64);
-                if (ok && (e & 3) == 0) {
-                    const int k = e >> 3, p = (e >> 2) & 1;
-                    const int q0 = quant_dc(d0 + d1 + d2 + d3, qc), q1 = quant_dc(d0 - d1 + d2 - d3, qc);
-                    const int q2 = quant_dc(d0 + d1 - d2 - d3, qc), q3 = quant_dc(d0 - d1 - d2 + d3, qc);
-                    lv[k * NPC + 16 + p] = make_uint4(((uint32_t)q0 & 0xffffu) | (uint32_t)q1 << 16,
-                                                      ((uint32_t)q2 & 0xffffu) | (uint32_t)q3 << 16, 0u, 0u);
-                    mt[k * NPC + 16 + p] =
-                        (uint16_t)((uint32_t)((q0 != 0) + (q1 != 0) + (q2 != 0) + (q3 != 0)) << 8);
-                }
-            }
-        };
-        /* two pixel sets in turn: the next pass's loads are in flight while
-         * this one is coded, with no register copies between passes */
-        for (int pa = 0; pa < np; ++pa) {                  /* pass 0's loads are in flight already */
-            const BlkPix cur = nx;
-            if (pa + 1 < np) issue(pa + 1, nx);
-            compute(pa, cur);
-        }
-#elif !defined(SCROLL_ROW_MFMA)
         /* round 6: a wave's passes are luma ones, then chroma ones, then
          * none (L0 and T are multiples of 64), so two loops whose kind is
          * known at compile time: no per-pass kind tests, and the compiler
@@ -1817,17 +1610,9 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             if (q < qL) issue_l(q, px);
             else issue_c(q, px);
         };
-        /* a level record: packed levels, TotalCoeff, its rank in its class
-         * (counting sort: the order inside a class does not matter) */
-#ifdef SCROLL_ROW_OLDREC
-        auto put_rec = [&](int slot, const uint32_t pk[4]) {
-            const int n = nz_bytes(pk[0]) + nz_bytes(pk[1]) + nz_bytes(pk[2]) + nz_bytes(pk[3]);
-            lv[slot] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-            mt[slot] = (uint16_t)((uint32_t)min(n, 16) << 8);
-            lo[slot] = (uint16_t)atomicAdd(&L.kc[0][SORT_KEYS - 1 - min(n, SORT_KEYS - 1)], 1u);
-        };
-#else
-        /* round 6: mt holds the block's non-zero mask until its CAVLC body
+        /* a level record: packed levels, the block's non-zero mask, its rank
+         * in its class (counting sort: the order inside a class does not
+         * matter).  mt holds the mask until the block's CAVLC body
          * (TotalCoeff = its popcount), so the body phase reads it instead of
          * deriving it from the levels again */
         const NzConst nzc = nz_const();
@@ -1840,12 +1625,8 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             /* a block without levels has no CAVLC body: no rank (its class
              * sorts last and is never read), and no same-address LDS atomic
              * of the many such lanes of a wave */
-#ifndef SCROLL_ROW_RANK_ALL
-            if (n)
-#endif
-                lo[slot] = (uint16_t)atomicAdd(&L.kc[0][SORT_KEYS - 1 - min(n, SORT_KEYS - 1)], 1u);
+            if (n) lo[slot] = (uint16_t)atomicAdd(&L.kc[0][SORT_KEYS - 1 - min(n, SORT_KEYS - 1)], 1u);
         };
-#endif
         /* the quantisers' bias pairs pinned in VGPRs (full-rate v_bitop3) */
         const LevelsBias bl = levels_bias(ql), bc = levels_bias(qc);
         auto code_l = [&](int q, const BlkPix &px) {
@@ -1872,27 +1653,11 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             levels_pk<false>(px.a, pr, pk, w0, qc, bc.k1, bc.k0);
             const bool ok = e < 8 * w;
             if (ok) put_rec((int)__umul24((uint32_t)(e >> 3), (uint32_t)NPC) + 18 + (e & 7), pk);
-#ifndef SCROLL_ROW_OLDREC
             /* chroma DC: the block's DC coefficient (|W0| <= 4080) as int16 i
              * of its plane's DC slot; the 2x2 Hadamard and quant follow the
              * loop, once per DC block (round 6: in the loop every chroma lane
              * ran them, masked to one lane of four) */
             if (ok) reinterpret_cast<int16_t *>(lv + (e >> 3) * NPC + 16 + ((e >> 2) & 1))[e & 3] = (int16_t)w0;
-#else
-            /* chroma DC: the quad's four DC coefficients -> 2x2 Hadamard,
-             * quant -> levels as int16 in the DC slot (quads are lane-aligned) */
-            const int qb = lane & ~3;
-            const int d0 = __shfl(w0, qb, 64), d1 = __shfl(w0, qb + 1, 64);
-            const int d2 = __shfl(w0, qb + 2, 64), d3 = __shfl(w0, qb + 3, 64);
-            if (ok && (e & 3) == 0) {
-                const int k = e >> 3, p = (e >> 2) & 1;
-                const int q0 = quant_dc(d0 + d1 + d2 + d3, qc), q1 = quant_dc(d0 - d1 + d2 - d3, qc);
-                const int q2 = quant_dc(d0 + d1 - d2 - d3, qc), q3 = quant_dc(d0 - d1 - d2 + d3, qc);
-                lv[k * NPC + 16 + p] = make_uint4(((uint32_t)q0 & 0xffffu) | (uint32_t)q1 << 16,
-                                                  ((uint32_t)q2 & 0xffffu) | (uint32_t)q3 << 16, 0u, 0u);
-                mt[k * NPC + 16 + p] = (uint16_t)((uint32_t)((q0 != 0) + (q1 != 0) + (q2 != 0) + (q3 != 0)) << 8);
-            }
-#endif
         };
         /* two pixel sets in fixed roles (the passes unrolled by two): pass
          * q + 1's loads go into one while pass q is coded from the other --
@@ -1918,123 +1683,6 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             code_c(q + 1, B);
         }
         if (q < qC) code_c(q, A);
-        (void)np;
-#else
-        /* round 6: the levels on the matrix cores (row_mfma.h, MFetch): per
-         * pass and wave 4 tiles of 16 blocks, each one MFMA, the quant of two
-         * tiles per asm block, a lane-group transpose, then one block per
-         * lane as before (put_rec).  The pass structure is the vector
-         * form's: luma passes, then chroma ones, the next pass's loads in
-         * flight while one is coded */
-        const int qL = nl > wv0 ? (nl - wv0 + T - 1) / T : 0;
-        const int qC = ntv > wv0 ? (ntv - wv0 + T - 1) / T : 0;
-        const int gq = lane >> 4, ln = lane & 15;
-        auto issue_l = [&](int q, MPix &px) { mfetch_pass(mo, false, (uint32_t)((q - mo.pb) * T), fs, rb, px); };
-        auto issue_c = [&](int q, MPix &px) {
-            if (!mo_chroma) {
-                mfetch_chroma(mo, q * T + wv0 - L0, r, g, csz, L.rt + 16, L.rt + 24, lane);
-                mo.pb = q;
-                mo_chroma = true;
-            }
-            mfetch_pass(mo, true, (uint32_t)((q - mo.pb) * T), fs, rb, px);
-        };
-        auto issue_any = [&](int q, MPix &px) {
-            if (q < qL) issue_l(q, px);
-            else issue_c(q, px);
-        };
-        auto put_rec = [&](int slot, const uint32_t pk[4]) {
-            const uint4 p4 = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-            const uint32_t nz = nz_mask16(p4);
-            const int n = __builtin_popcount(nz);
-            lv[slot] = p4;
-            mt[slot] = (uint16_t)nz;
-            /* a block without levels has no CAVLC body: no rank (its class
-             * sorts last and is never read), and no same-address LDS atomic
-             * of the many such lanes of a wave */
-#ifndef SCROLL_ROW_RANK_ALL
-            if (n)
-#endif
-                lo[slot] = (uint16_t)atomicAdd(&L.kc[0][SORT_KEYS - 1 - min(n, SORT_KEYS - 1)], 1u);
-        };
-        const uint64_t aL = g_kmat.a[0][lane];
-        const MQuant QL = mquant_of(gq, true, ql);
-        auto code_l = [&](int q, const MPix &px) {
-            uint32_t wd[4];
-            {
-                const mfma_v4i d0 = mtile(aL, px.s.x, px.p.x), d1 = mtile(aL, px.s.y, px.p.y);
-                mquant2(d0, d1, QL, wd[0], wd[1]);
-            }
-            {
-                const mfma_v4i d2 = mtile(aL, px.s.z, px.p.z), d3 = mtile(aL, px.s.w, px.p.w);
-                mquant2(d2, d3, QL, wd[2], wd[3]);
-            }
-            mtranspose(wd);
-            /* lane (gq, ln): block (MB ln / 4 of the pass's four, row ln % 4, column gq) */
-            const int k = ((q * T + wv0) >> 4) + (ln >> 2);
-            if (k < w) put_rec((int)__umul24((uint32_t)k, (uint32_t)NPC) + 4 * (ln & 3) + gq, wd);
-        };
-        auto code_c = [&](int q, const MPix &px, uint64_t aC, const MQuant &QC) {
-            uint32_t pr[4];
-            const uint32_t up[4] = {px.p.x, px.p.y, px.p.z, px.p.w}, dn[4] = {px.q.x, px.q.y, px.q.z, px.q.w};
-            if (frc == 4u) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pr[j] = __builtin_amdgcn_lerp(up[j], dn[j], 0x01010101u);
-            } else if (frc == 0u) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pr[j] = up[j];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pr[j] = bilin4(up[j], dn[j], frc);
-            }
-            const mfma_v4i d0 = mtile(aC, px.s.x, pr[0]), d1 = mtile(aC, px.s.y, pr[1]);
-            const mfma_v4i d2 = mtile(aC, px.s.z, pr[2]), d3 = mtile(aC, px.s.w, pr[3]);
-            const int kb = ((q * T + wv0 - L0) >> 3) + 2 * (ln & 3), pl = ln >> 3, by = (ln >> 2) & 1;
-            /* the DC coefficients (row 15, lane group 3) as int16 into their
-             * plane's DC slot: tile j = MB kb + j / 2, block column j % 2 */
-            if (gq == 3) {
-                const int dcv[4] = {d0[3], d1[3], d2[3], d3[3]};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int k = kb + (j >> 1);
-                    if (k < w)
-                        reinterpret_cast<int16_t *>(lv + (int)__umul24((uint32_t)k, (uint32_t)NPC) + 16 + pl)[2 * by + (j & 1)] =
-                            (int16_t)dcv[j];
-                }
-            }
-            uint32_t wd[4];
-            mquant2(d0, d1, QC, wd[0], wd[1]);
-            mquant2(d2, d3, QC, wd[2], wd[3]);
-            mtranspose(wd);
-            const int k = kb + (gq >> 1);
-            if (k < w) put_rec((int)__umul24((uint32_t)k, (uint32_t)NPC) + 18 + 4 * pl + 2 * by + (gq & 1), wd);
-        };
-        MPix A = mx, B;
-        int q = 0;
-        for (; q + 1 < qL; q += 2) {
-            issue_l(q + 1, B);
-            code_l(q, A);
-            issue_any(q + 2, A);
-            code_l(q + 1, B);
-        }
-        if (q < qL) {                                       /* an odd luma pass left */
-            issue_any(q + 1, B);
-            code_l(q, A);
-            A = B;                                          /* once: the first chroma pass */
-            ++q;
-        }
-        if (q < qC) {
-            const uint64_t aC = g_kmat.a[1][lane];
-            const MQuant QC = mquant_of(gq, false, qc);
-            for (; q + 1 < qC; q += 2) {
-                issue_c(q + 1, B);
-                code_c(q, A, aC, QC);
-                issue_c(q + 2, A);                          /* past the tasks: unused loads */
-                code_c(q + 1, B, aC, QC);
-            }
-            if (q < qC) code_c(q, A, aC, QC);
-        }
-        (void)np;
-#endif
         __syncthreads();                                /* levels, TotalCoeffs, ptabs, counts */
         if (stp) stp[1] = __builtin_amdgcn_s_memrealtime();
         /* the row's bottom TotalCoeffs (luma 12-15, chroma AC raster 2, 3 of
@@ -2046,11 +1694,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int pcA = e < 4 ? 12 + e : (e < 6 ? 16 + e : 18 + e);
-#ifdef SCROLL_ROW_OLDREC
-                v |= (uint64_t)(tc_of(mk[pcA]) & 31) << (5 * e);
-#else
                 v |= (uint64_t)__builtin_popcount(mk[pcA]) << (5 * e);    /* the block's non-zero mask */
-#endif
             }
             lb_store(tcx + (nb * R.h + r) * (size_t)w + t, (uint64_t)(epoch & 0xffffffu) << 40 | v);
         }
@@ -2069,27 +1713,13 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         }
         for (int task = t; task < ntask; task += T) {       /* the slot, chroma flagged in bit 15 */
             const int slot = row_slot(task, w);
-#ifdef SCROLL_ROW_OLDREC
-            const int tcs = tc_of(mt[slot]);
-#else
             const int tcs = __builtin_popcount(mt[slot]);
-#endif
             if (tcs) {
                 order[L.kc[1][SORT_KEYS - 1 - min(tcs, SORT_KEYS - 1)] + lo[slot]] =
                     (uint16_t)(slot | (task < 16 * w ? 0 : 0x8000));
-#if SCROLL_LV_SWZ
-                /* the record's dwords swizzled by its slot (lv_key): the
-                 * CAVLC lanes read one level byte each from records on
-                 * about consecutive slots (the sort's ranks follow the
-                 * lanes), 16 bytes apart -- four banks -- so lanes 16 slots
-                 * apart met in one bank; with dword d at d ^ key they don't */
-                const uint32_t key = lv_key(slot);
-                if (key) lv[slot] = lv_swz(lv[slot], key);
-#endif
             }
         }
         __syncthreads();
-    ROW_CUT(1);
         /* CAVLC bodies, largest TotalCoeff first */
         const int zbase = (int)L.kc[1][SORT_KEYS - 1];      /* blocks without levels sort last: no body */
         for (int pa = 0; pa < np; ++pa) {
@@ -2103,19 +1733,12 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             bool ok = true;
             /* total_zeros + run_before from the table: the load is in flight
              * during the trailing ones and the level loop */
-#ifdef SCROLL_ROW_OLDREC
-            const uint32_t nz = nz_mask16(lv[slot]);
-#else
             const uint32_t nz = mt[slot];                   /* the non-zero mask (levels phase) */
-#endif
             const uint32_t tzrb = g_tzrb[luma ? nz : 65536u + nz];
-            const uint32_t key = SCROLL_LV_SWZ ? lv_key(slot) : 0u;
-            const int tc = cavlc_body_t(cap, reinterpret_cast<const int8_t *>(lv + slot), nz, tzrb, t1, ok, L.lvt,
-                                        key << 2);
+            const int tc = cavlc_body_t(cap, reinterpret_cast<const int8_t *>(lv + slot), nz, tzrb, t1, ok, L.lvt);
             mt[slot] = ok ? (uint16_t)(cap.n | (uint32_t)tc << 8 | (uint32_t)t1 << 13)
                           : (uint16_t)((uint32_t)tc << 8 | (uint32_t)t1 << 13 | M_OVF);
-            if (ok) lv[slot] = body_msb(cap.hi, cap.lo, cap.n);
-            else if (key) lv[slot] = lv_swz(lv[slot], key);     /* rare: the levels stay, in plain order */
+            if (ok) lv[slot] = body_msb(cap.hi, cap.lo, cap.n);     /* else, rare: the levels stay */
         }
         /* chroma DC blocks, whole (nC = -1): their slots (k NPC + 16 + p of
          * mt / lv) are no block task's, so nothing reads them before the
@@ -2126,17 +1749,12 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         for (int i = dcT - 1 - t; i >= 0 && i < 2 * w; i += dcT) {
             const int k = i >> 1, p = i & 1, sl = k * NPC + 16 + p;
             const uint4 q = lv[sl];
-#ifdef SCROLL_ROW_OLDREC
-            const int dq[4] = {(int)(int16_t)(q.x & 0xffffu), (int)(int16_t)(q.x >> 16),
-                               (int)(int16_t)(q.y & 0xffffu), (int)(int16_t)(q.y >> 16)};
-#else
             /* the four DC coefficients of the plane's 4x4 blocks (raster) ->
              * 2x2 Hadamard, quant (qbits + 1) */
             const int d0 = (int)(int16_t)(q.x & 0xffffu), d1 = (int)(int16_t)(q.x >> 16);
             const int d2 = (int)(int16_t)(q.y & 0xffffu), d3 = (int)(int16_t)(q.y >> 16);
             const int dq[4] = {quant_dc(d0 + d1 + d2 + d3, qc), quant_dc(d0 - d1 + d2 - d3, qc),
                                quant_dc(d0 + d1 - d2 - d3, qc), quant_dc(d0 - d1 - d2 + d3, qc)};
-#endif
             CapSink cap{0, 0, 0};
             const int tc = cavlc_dc4(cap, L.ptabs, dq);
             if (cap.n <= 128) {
@@ -2144,10 +1762,8 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
                 lv[sl] = body_msb(cap.hi, cap.lo, cap.n);
             } else {
                 mt[sl] = (uint16_t)((uint32_t)tc << 8 | M_OVF);       /* the levels in lv */
-#ifndef SCROLL_ROW_OLDREC
                 lv[sl] = make_uint4(((uint32_t)dq[0] & 0xffffu) | (uint32_t)dq[1] << 16,
                                     ((uint32_t)dq[2] & 0xffffu) | (uint32_t)dq[3] << 16, 0u, 0u);
-#endif
             }
         }
     } else {
@@ -2224,7 +1840,6 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     };
     __syncthreads();                                    /* records, top TotalCoeffs, waypoint table */
     if (stp) stp[2] = __builtin_amdgcn_s_memrealtime();
-    ROW_CUT(2);
 
     /* ---- 3: coeff_token, piece lengths ----------------------------------- */
     const Tabs &TB = g_tabs;
@@ -2276,7 +1891,6 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     }
     __syncthreads();
     if (stp) stp[3] = __builtin_amdgcn_s_memrealtime();
-    ROW_CUT(3);
     const bool head_over = L.head_over;
     auto head_bits = [&](int rr, int col) -> uint32_t {
         if (!head_over) return L.hlen[H.sel(rr, col)];
@@ -2389,7 +2003,6 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         __syncthreads();
     }
     if (stp) stp[4] = __builtin_amdgcn_s_memrealtime();
-    ROW_CUT(4);
     const uint32_t bits = colpos(mbw);
     if (t == 0) gbits[nb * (size_t)ng + gi] = bits;
 

@@ -109,9 +109,10 @@ typedef struct {
     uint32_t bmv[16];
 } SpliceMbRec;
 #define SPLICE_REC_HEAD 96
-/* RBSP word pools: words past the last unit that k_splice_stage's body
- * reader may load (splice_kernels.hip RWin) */
-#define RWIN_SLACK_WORDS 8
+/* RBSP word pools: spare words past the last unit.  k_splice_stage's body
+ * reader (splice_kernels.hip put_rbsp -> bits_at) loads one word past the
+ * word holding a body's last bit */
+#define RBSP_SLACK_WORDS 8
 
 
 /* 0, or -1 when the launch failed */

@@ -2002,9 +2002,6 @@ __global__ __launch_bounds__(64) void k_splice_fix(int n, const int32_t *__restr
 /* k_splice_stage                                                            */
 /* ------------------------------------------------------------------------ */
 constexpr int SPL_WB = 2048;                 /* writing sweep: LDS words per pass (64 Kbit) */
-#ifndef SCROLL_STAGE_HEAD_LDS
-#define SCROLL_STAGE_HEAD_LDS 1
-#endif
 
 /* ORs MSB-first words into LDS words [lo, lo + n) (others dropped: another pass) */
 struct LdsWin {
@@ -2033,11 +2030,9 @@ struct SpliceLds {
     uint32_t ep_n;
     int32_t bad;
     uint32_t carry;                         /* the partial word at the bit position (MSB first) */
-#if SCROLL_STAGE_HEAD_LDS
     /* each lane's spliced MB record head (SPLICE_REC_HEAD bytes): held in
      * registers across the window it took the kernel to 252 VGPRs */
     alignas(16) uint8_t hdb[DT][SPLICE_REC_HEAD];
-#endif
 };
 static_assert(offsetof(SpliceMbRec, bl) == SPLICE_REC_HEAD && sizeof(SpliceMbRec) == 232,
               "the stage copies a record's first SPLICE_REC_HEAD bytes in 16-byte loads");
@@ -2090,60 +2085,14 @@ struct GlobOr {
 };
 typedef OrSink<GlobOr> GSink;
 
-/* n <= 32 bits at bit offset q of the RBSP words */
+/* n <= 32 bits at bit offset q of the RBSP words (with q a multiple of 32
+ * only w[k] is read; else also w[k + 1], which may lie past the unit's last
+ * bit: the word pools keep RBSP_SLACK_WORDS after their last unit) */
 __device__ inline uint32_t bits_at(const uint32_t *w, uint32_t q)
 {
     const uint32_t k = q >> 5, o = q & 31u;
     return o ? (w[k] << o) | (w[k + 1] >> (32u - o)) : w[k];
 }
-
-#ifndef SCROLL_STAGE_BL_PRELOAD
-#define SCROLL_STAGE_BL_PRELOAD 1
-#endif
-/* SCROLL_STAGE_RWIN=1 (measured, not kept): the body reader below --
- * p720splicerows 5.09 -> 5.16 ms per step (profiles/r06s_stage_rwin.txt) */
-#ifndef SCROLL_STAGE_RWIN
-#define SCROLL_STAGE_RWIN 0
-#endif
-
-/* the writing sweep's reader of an MB's piece bodies: six RBSP words from
- * word wb in registers, moved on one word as a read passes word wb, the
- * word loaded then five words ahead -- the loads run ahead of the bits
- * instead of one load round trip per body, and a read always takes w0 / w1
- * (no selects: a select chain over the six became a scratch copy indexed
- * per lane).  Reads up to 6 words past the MB's last bit: the word pools
- * keep RWIN_SLACK_WORDS after their last unit */
-static_assert(RWIN_SLACK_WORDS >= 6, "RWin reads up to 6 words past an MB's last bit");
-struct RWin {
-    const uint32_t *rb;
-    uint32_t wb, w0, w1, w2, w3, w4, w5;
-    __device__ inline void init(const uint32_t *r, uint32_t q)
-    {
-        rb = r;
-        wb = q >> 5;
-        w0 = rb[wb];
-        w1 = rb[wb + 1];
-        w2 = rb[wb + 2];
-        w3 = rb[wb + 3];
-        w4 = rb[wb + 4];
-        w5 = rb[wb + 5];
-    }
-    /* the 32 bits from bit q (q >= 32 wb), MSB first */
-    __device__ inline uint32_t at(uint32_t q)
-    {
-        while ((q >> 5) > wb) {
-            w0 = w1;
-            w1 = w2;
-            w2 = w3;
-            w3 = w4;
-            w4 = w5;
-            w5 = rb[wb + 6];
-            ++wb;
-        }
-        const uint32_t o = q & 31u;
-        return o ? __builtin_amdgcn_alignbit(w0, w1, 32u - o) : w0;
-    }
-};
 
 /* n bits at bit q of the RBSP words, put */
 template <class SK>
@@ -2198,7 +2147,6 @@ __device__ inline void splice_tail(SK &sk, const SpliceMbRec &h, const SpliceMbR
     /* the pieces' u16 words, all at once (7 8-byte loads; records are 8-byte
      * aligned): per piece only its body's bit loads remain on the chain */
     uint32_t blw[(SPLICE_PIECES + 1) / 2] = {};
-#if SCROLL_STAGE_BL_PRELOAD
     if constexpr (!count) {
         const uint2 *bq = reinterpret_cast<const uint2 *>(R->bl);
 #pragma unroll
@@ -2207,11 +2155,6 @@ __device__ inline void splice_tail(SK &sk, const SpliceMbRec &h, const SpliceMbR
             blw[2 * q] = v.x;
             blw[2 * q + 1] = v.y;
         }
-    }
-#endif
-    RWin win;
-    if constexpr (!count) {
-        if (SCROLL_STAGE_RWIN) win.init(rb, rp);
     }
     auto piece = [&](int i, int nC) {
         const int tc = h.tc[i], t1 = h.t1[i];
@@ -2226,17 +2169,10 @@ __device__ inline void splice_tail(SK &sk, const SpliceMbRec &h, const SpliceMbR
         }
         sk.put(v, (int)len);
         if constexpr (!count) {
-            const uint32_t e = SCROLL_STAGE_BL_PRELOAD ? (blw[i >> 1] >> (16 * (i & 1))) & 0xffffu : R->bl[i];
+            const uint32_t e = (blw[i >> 1] >> (16 * (i & 1))) & 0xffffu;
             rp += e >> 11;                      /* past its external coeff_token */
             const uint32_t n = e & 2047u;
-            if (SCROLL_STAGE_RWIN) {
-                for (uint32_t k = 0; k < n; k += 32) {
-                    const int c = (int)min(32u, n - k);
-                    sk.put(win.at(rp + k) >> (32 - c), c);
-                }
-            } else {
-                put_rbsp(sk, rb, rp, n);
-            }
+            put_rbsp(sk, rb, rp, n);
             rp += n;
         }
     };
@@ -2353,11 +2289,7 @@ __global__ __launch_bounds__(DT) __attribute__((amdgpu_waves_per_eu(SCROLL_STAGE
         int x = 0, y = 0, k = -1;
         Mv me{0, 0, 0};
         bool parted = false;
-#if SCROLL_STAGE_HEAD_LDS
-        SpliceMbRec &hd = *reinterpret_cast<SpliceMbRec *>(L.hdb[t]);   /* its head only */
-#else
-        SpliceMbRec hd;                                        /* a spliced MB's record head */
-#endif
+        SpliceMbRec &hd = *reinterpret_cast<SpliceMbRec *>(L.hdb[t]);   /* a spliced MB's record head only */
         uint4 et = make_uint4(0u, 0u, 0u, 0u);
         if (m < nmb) {
             y = (int)div_m((uint32_t)m, m_mbw);
@@ -2365,15 +2297,8 @@ __global__ __launch_bounds__(DT) __attribute__((amdgpu_waves_per_eu(SCROLL_STAGE
             if (x >= SF.x0 && x < SF.x0 + SF.w && y >= SF.y0 && y < SF.y0 + SF.h) {
                 k = (y - SF.y0) * SF.w + (x - SF.x0);
                 const uint4 *hp = reinterpret_cast<const uint4 *>(rec + k);
-#if SCROLL_STAGE_HEAD_LDS
 #pragma unroll
                 for (int q = 0; q < SPLICE_REC_HEAD / 16; ++q) reinterpret_cast<uint4 *>(L.hdb[t])[q] = hp[q];
-#else
-                uint4 hv[SPLICE_REC_HEAD / 16];
-#pragma unroll
-                for (int q = 0; q < SPLICE_REC_HEAD / 16; ++q) hv[q] = hp[q];
-                __builtin_memcpy(&hd, hv, SPLICE_REC_HEAD);
-#endif
                 if (SF.hd_qp >= 0)                             /* the dynamic rect under hints: its QP chain */
                     hd.qpd = (int8_t)((uint32_t)k == SF.hd_first ? SF.hd_qp - 26 : 0);
                 et = edge_tc(hd);

@@ -1,6 +1,6 @@
 #!/bin/bash
 # build_variant.sh NAME "HIPDEFS" -- a profiling variant of libh264scroll.so
-# (e.g. -DSCROLL_ABL_STOP=2) in variants/NAME/ (git-ignored; travels to the
+# (e.g. -DSCROLL_ROW_NP=4) in variants/NAME/ (git-ignored; travels to the
 # GPU box with the tree).  Select it with H264SCROLL_LIB=variants/NAME/libh264scroll.so.
 set -e
 HERE=$(cd "$(dirname "$0")/.." && pwd)

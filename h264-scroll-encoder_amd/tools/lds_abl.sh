@@ -1,6 +1,6 @@
 #!/bin/bash
 # lds_abl.sh OUTDIR VARIANT... -- per library variant (build_variant.sh, e.g.
-# the -DSCROLL_ABL_STOP=n phase cuts) and the tree's build ("cur"): one
+# -DSCROLL_ROW_NP=4) and the tree's build ("cur"): one
 # counter pass over a p720dyn bench step -- LDS instructions, bank-conflict
 # and LDS-active cycles, LDS waits, vector-memory loads, texture address /
 # data busy.  Each run has its own time limit; the first failure ends it.

@@ -62,8 +62,8 @@ extern "C" {
 #define SCROLL_DEBUG_EMIT_NOBYTES 128 /* k_emit skips the tile-end partial chunks  */
 #define SCROLL_DEBUG_DYN_STAMPS 256 /* k_dyn_row / gather: realtime per phase    */
 /* retired: runtime ablations of the earlier one-kernel dynamic coder (no
- * kernel reads them now; k_dyn_row's per-phase ablation is the compile-time
- * variant -DSCROLL_ABL_STOP=n).  Values kept so the flag numbering stays
+ * kernel reads them now; k_dyn_row's per-phase times come from
+ * SCROLL_DEBUG_DYN_STAMPS).  Values kept so the flag numbering stays
  * stable. */
 #define SCROLL_DEBUG_DYN_NOLOAD  512
 #define SCROLL_DEBUG_DYN_NOCAVLC 1024
