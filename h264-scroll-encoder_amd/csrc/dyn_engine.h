@@ -39,6 +39,15 @@ typedef struct {
     hipStream_t side;
     hipEvent_t e0, e1;
 } DynFork;
+/* k_dyn_rows alone: every frame's prediction rows (rows: 32 h u32 per
+ * frame), MB-head classes (heads: DYN_HEAD_VECS per frame) and, in ctr
+ * ([1] and the list from DYN_CTR_LIST, zeroed by k_plan's state pass), the
+ * frames with a row on the general path, of which g->gen_cap fit.  It writes
+ * DynFrame.rbsp_bytes / ep / err of dfr and nothing else: the QP probe runs
+ * it into buffers of its own */
+int dyn_launch_rows(hipStream_t hs, int nframes, int S, const DevStream *st, const NalDesc *nal, int ld_nal,
+                    const PlanPending *pend, DynFrame *dfr, int ld_fr, const DynGeom *g, uint32_t *rows,
+                    uint32_t *ctr, uint4 *heads);
 /* k_dyn_rows + k_dyn_code_general (records of the general-path NALs) +
  * k_dyn_row (every rect row: block coding + packing -> its row-stage bits);
  * fk != NULL: the fork above (k_dyn_static then runs on the side stream);

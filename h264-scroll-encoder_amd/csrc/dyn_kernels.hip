@@ -3660,6 +3660,16 @@ __global__ __launch_bounds__(256) void k_dyn_synth(uint8_t *__restrict__ src, Dy
 /* ---------------------------------------------------------------------- */
 /* launchers (engine-internal, engine.h)                                   */
 /* ---------------------------------------------------------------------- */
+int dyn_launch_rows(hipStream_t hs, int nframes, int S, const DevStream *st, const NalDesc *nal, int ld_nal,
+                    const PlanPending *pend, DynFrame *dfr, int ld_fr, const DynGeom *g, uint32_t *rows,
+                    uint32_t *ctr, uint4 *heads)
+{
+    if (nframes <= 0 || S <= 0) return 0;
+    hipLaunchKernelGGL(k_dyn_rows, dim3(nframes, S), dim3(256), 0, hs, st, nal, ld_nal, pend, dfr, ld_fr,
+                       *g, rows, ctr, heads);
+    return hipGetLastError() != hipSuccess ? -1 : 0;
+}
+
 int dyn_launch_code(hipStream_t hs, int nframes, int S, DevStream *st, const NalDesc *nal,
                     int ld_nal, const PlanPending *pend, DynFrame *dfr, int ld_fr,
                     const DynGeom *g, const uint8_t *src, const uint8_t *refs, const DynScratch *x,
@@ -3678,9 +3688,7 @@ int dyn_launch_code(hipStream_t hs, int nframes, int S, DevStream *st, const Nal
             ready |= 1ull << dev;
         }
     }
-    hipLaunchKernelGGL(k_dyn_rows, dim3(nframes, S), dim3(256), 0, hs, st, nal, ld_nal, pend, dfr, ld_fr,
-                       *g, x->rows, x->ctr, x->heads);
-    if (hipGetLastError() != hipSuccess) return -1;
+    if (dyn_launch_rows(hs, nframes, S, st, nal, ld_nal, pend, dfr, ld_fr, g, x->rows, x->ctr, x->heads)) return -1;
     hipStream_t hg = hs;                /* the general path's stream */
     if (fk) {
         if (hipEventRecord(fk->e0, hs) != hipSuccess || hipStreamWaitEvent(fk->side, fk->e0, 0) != hipSuccess)

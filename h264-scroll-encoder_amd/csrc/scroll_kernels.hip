@@ -23,6 +23,7 @@
 #include "dyn_engine.h"
 #include "recon_engine.h"
 #include "hrecon_engine.h"
+#include "probe_engine.h"
 #include "hint_engine.h"
 #include "splice_engine.h"
 #include "hdyn_engine.h"
@@ -938,6 +939,21 @@ struct ScrollBatch {
     int recon_hinted = 0;
     int rc_last_hint = 0;              /* the last compose ran k_hdyn_recon                  */
     std::vector<int> rc_fail;          /* [stream]: the status scroll_batch_sync reported for that compose */
+    /* the QP probe (scroll_batch_dyn_probe, probe_kernels.hip): a trial plan
+     * and its prediction rows in buffers of its own, so that nothing of the
+     * batch's state is touched; allocated by the first probe */
+    struct Probe {
+        NalDesc *nal = nullptr;
+        DynFrame *dfr = nullptr;
+        PlanPending *pend = nullptr;
+        uint32_t *rows = nullptr, *ctr = nullptr, *done = nullptr;
+        uint4 *heads = nullptr;
+        ScrollDynProbe *res = nullptr;  /* [max_streams * max_frames][SCROLL_DYN_PROBE_MAX_QPS] */
+        int nframes = -1, nstreams = 0, nq = 0;   /* the last probe; nframes -1: none */
+        hipEvent_t fin = nullptr;       /* recorded after the last probe's launches */
+        hipEvent_t ev[2] = {};          /* timing: around them (created on first use) */
+        int timed = 0;
+    } pb;
     /* UI hints: staged like the dynamic rect (shares
      * d_dfr, d_stage and geo.slot_bytes; the two are exclusive) */
     int hint_on = 0;
@@ -1126,6 +1142,8 @@ int scroll_batch_create(ScrollBatch **out, const ScrollBatchDesc *desc)
     return SCROLL_OK;
 }
 
+static void probe_release(ScrollBatch *b);
+
 void scroll_batch_destroy(ScrollBatch *b)
 {
     if (!b) return;
@@ -1158,6 +1176,7 @@ void scroll_batch_destroy(ScrollBatch *b)
     (void)hipFree(b->d_sse);
     for (hipEvent_t e : b->rc_ev)
         if (e) (void)hipEventDestroy(e);
+    probe_release(b);
     (void)hipFree(b->d_hf);
     (void)hipFree(b->d_pool);
     (void)hipFree(b->d_spf);
@@ -1965,8 +1984,30 @@ long long scroll_batch_last_nals(ScrollBatch *b)
 }
 
 /* ------------------------------ dynamic rect ----------------------------- */
+/* the probe's buffers go with the rect they were sized for */
+static void probe_release(ScrollBatch *b)
+{
+    ScrollBatch::Probe &p = b->pb;
+    if (p.fin) {
+        (void)hipEventSynchronize(p.fin);
+        (void)hipEventDestroy(p.fin);
+    }
+    for (hipEvent_t e : p.ev)
+        if (e) (void)hipEventDestroy(e);
+    (void)hipFree(p.nal);
+    (void)hipFree(p.dfr);
+    (void)hipFree(p.pend);
+    (void)hipFree(p.rows);
+    (void)hipFree(p.ctr);
+    (void)hipFree(p.done);
+    (void)hipFree(p.heads);
+    (void)hipFree(p.res);
+    p = ScrollBatch::Probe{};
+}
+
 static void dyn_release(ScrollBatch *b)
 {
+    probe_release(b);
     if (!b->hint_on) {                 /* else they are the hint path's */
         (void)hipFree(b->d_dfr);
         (void)hipFree(b->d_stage);
@@ -2469,6 +2510,157 @@ float scroll_batch_dyn_recon_ms(ScrollBatch *b)
     if (batch_host_sync(b)) return -1.0f;
     float ms = -1.0f;
     if (hipEventElapsedTime(&ms, b->rc_ev[0], b->rc_ev[1]) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1.0f;
+    }
+    return ms;
+}
+
+/* ------------------- probing the rect at candidate QPs -------------------- */
+static int probe_alloc(ScrollBatch *b)
+{
+    ScrollBatch::Probe &p = b->pb;
+    if (p.res) return SCROLL_OK;
+    const size_t S = (size_t)b->max_streams, NF = S * (size_t)b->max_frames;
+    hipError_t e = hipMalloc(&p.nal, S * (size_t)b->ld_nal * sizeof(NalDesc));
+    if (e == hipSuccess) e = hipMalloc(&p.dfr, NF * sizeof(DynFrame));
+    if (e == hipSuccess) e = hipMalloc(&p.pend, S * sizeof(PlanPending));
+    if (e == hipSuccess) e = hipMalloc(&p.rows, NF * 32 * (size_t)b->geo.h * sizeof(uint32_t));
+    /* the general-frame list holds every frame: it can never run out */
+    if (e == hipSuccess) e = hipMalloc(&p.ctr, (DYN_CTR_LIST + NF) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&p.done, NF * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&p.heads, NF * DYN_HEAD_VECS * sizeof(uint4));
+    if (e == hipSuccess) e = hipMalloc(&p.res, NF * SCROLL_DYN_PROBE_MAX_QPS * sizeof(ScrollDynProbe));
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&p.fin, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        set_err("scroll_batch_dyn_probe: %s", hipGetErrorString(e));
+        probe_release(b);
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory ? SCROLL_ERR_OOM : SCROLL_ERR_HIP;
+    }
+    return SCROLL_OK;
+}
+
+int scroll_batch_dyn_probe(ScrollBatch *b, int nframes, const uint8_t *qps, int nq, void *hip_stream)
+{
+    if (!b || !qps || nq < 1 || nq > SCROLL_DYN_PROBE_MAX_QPS) {
+        set_err("scroll_batch_dyn_probe: 1..%d candidate QPs", SCROLL_DYN_PROBE_MAX_QPS);
+        return SCROLL_ERR_ARG;
+    }
+    if (nframes < 0 || nframes > b->max_frames) {
+        set_err("scroll_batch_dyn_probe: nframes %d out of range", nframes);
+        return SCROLL_ERR_ARG;
+    }
+    ProbeQps Q{};
+    Q.n = nq;
+    for (int k = 0; k < nq; ++k) {
+        if (qps[k] > 51) {
+            set_err("scroll_batch_dyn_probe: candidate %d: QP %d outside 0..51", k, qps[k]);
+            return SCROLL_ERR_ARG;
+        }
+        Q.qp[k] = qps[k];
+    }
+    if (!b->dyn_on || !b->dyn_refs) {
+        set_err("scroll_batch_dyn_probe: needs a dynamic rect with reference pictures "
+                "(scroll_batch_set_dyn_rect, scroll_batch_set_dyn_refs)");
+        return SCROLL_ERR_CONFIG;
+    }
+    if (b->hint_on) {
+        set_err("scroll_batch_dyn_probe: covers the plain dynamic rect, not the rect under UI hints: "
+                "clear the hints");
+        return SCROLL_ERR_CONFIG;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    int rc = probe_alloc(b);
+    if (rc) return rc;
+    ScrollBatch::Probe &p = b->pb;
+    hipStream_t hs = hip_stream ? (hipStream_t)hip_stream : b->own;
+    const int S = b->nstreams, ld_fr = b->max_frames;
+    p.nframes = nframes;
+    p.nstreams = S;
+    p.nq = nq;
+    p.timed = 0;
+    if (S > 0 && nframes > 0) {
+        const bool timed = b->timing != 0;
+        if (timed && !p.ev[0]) {
+            HIPCHK(hipEventCreate(&p.ev[0]));
+            HIPCHK(hipEventCreate(&p.ev[1]));
+        }
+        if (timed) HIPCHK(hipEventRecord(p.ev[0], hs));
+        /* the compose's state pass and k_dyn_rows, into the probe's own
+         * NalDesc / DynFrame / PlanPending / rows / heads / ctr: k_plan with
+         * PLAN_STATE reads the streams and commits nothing */
+        DynGeom G = b->geo;
+        G.debug = b->debug;
+        G.gen_cap = (uint32_t)((size_t)b->max_streams * ld_fr);
+        const int plan = b->mode == SCROLL_MODE_EXPERIMENT ? SCROLL_PLAN_EXPERIMENT : SCROLL_PLAN_COMPOSER;
+        hipLaunchKernelGGL(k_plan, dim3(S), dim3(PLAN_THREADS), 0, hs, b->d_st, b->d_off, b->max_frames, p.nal,
+                           b->ld_nal, nframes, plan, b->debug | PLAN_STATE | PLAN_DYN, p.pend, p.dfr, ld_fr,
+                           nullptr, 0u, 0u, p.ctr);
+        HIPCHK(hipGetLastError());
+        if (dyn_launch_rows(hs, nframes, S, b->d_st, p.nal, b->ld_nal, p.pend, p.dfr, ld_fr, &G, p.rows, p.ctr,
+                            p.heads)) {
+            set_err("k_dyn_rows launch: %s", hipGetErrorString(hipGetLastError()));
+            return SCROLL_ERR_HIP;
+        }
+        if (probe_launch(hs, nframes, S, b->d_st, p.nal, b->ld_nal, p.pend, p.dfr, ld_fr, &G, p.rows, b->d_src,
+                         b->d_refs, &Q, p.res, p.done, p.ctr, nullptr, timed ? p.ev[1] : nullptr)) {
+            set_err("k_dyn_probe launch: %s", hipGetErrorString(hipGetLastError()));
+            return SCROLL_ERR_HIP;
+        }
+        p.timed = timed ? 1 : 0;
+    }
+    HIPCHK(hipEventRecord(p.fin, hs));
+    return SCROLL_OK;
+}
+
+int scroll_batch_dyn_probe_result(ScrollBatch *b, int s, int f, int k, ScrollDynProbe *out)
+{
+    if (!b || !out) return SCROLL_ERR_ARG;
+    ScrollBatch::Probe &p = b->pb;
+    if (!p.res || p.nframes < 0) {
+        set_err("scroll_batch_dyn_probe_result: no probe to read (scroll_batch_dyn_probe; "
+                "scroll_batch_set_dyn_rect drops it)");
+        return SCROLL_ERR_CONFIG;
+    }
+    if (s < 0 || s >= p.nstreams || f < 0 || f >= p.nframes || k < 0 || k >= p.nq) {
+        set_err("scroll_batch_dyn_probe_result: stream %d / frame %d / candidate %d outside the last probe", s, f, k);
+        return SCROLL_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipEventSynchronize(p.fin));
+    const size_t fi = (size_t)s * b->max_frames + f;
+    DynFrame d;
+    HIPCHK(hipMemcpy(&d, p.dfr + fi, sizeof(d), hipMemcpyDeviceToHost));
+    if (d.nal < 0) return 1;
+    uint32_t rows_in = 0;
+    HIPCHK(hipMemcpy(&rows_in, p.done + fi, sizeof(rows_in), hipMemcpyDeviceToHost));
+    if (rows_in != (uint32_t)b->geo.h) {
+        set_err("scroll_batch_dyn_probe_result: stream %d frame %d: %u of %d rect rows counted", s, f, rows_in,
+                b->geo.h);
+        return SCROLL_ERR_DEVICE;
+    }
+    HIPCHK(hipMemcpy(out, p.res + fi * SCROLL_DYN_PROBE_MAX_QPS + k, sizeof(*out), hipMemcpyDeviceToHost));
+    return SCROLL_OK;
+}
+
+const ScrollDynProbe *scroll_batch_dyn_probe_device(ScrollBatch *b, size_t *stream_stride, size_t *frame_stride)
+{
+    if (!b || !b->pb.res) return nullptr;
+    if (frame_stride) *frame_stride = SCROLL_DYN_PROBE_MAX_QPS * sizeof(ScrollDynProbe);
+    if (stream_stride) *stream_stride = (size_t)b->max_frames * SCROLL_DYN_PROBE_MAX_QPS * sizeof(ScrollDynProbe);
+    return b->pb.res;
+}
+
+float scroll_batch_dyn_probe_ms(ScrollBatch *b)
+{
+    if (!b || !b->pb.res || !b->pb.timed) return -1.0f;
+    if (hipEventSynchronize(b->pb.ev[1]) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1.0f;
+    }
+    float ms = -1.0f;
+    if (hipEventElapsedTime(&ms, b->pb.ev[0], b->pb.ev[1]) != hipSuccess) {
         (void)hipGetLastError();
         return -1.0f;
     }

@@ -126,6 +126,13 @@ SCROLL_HINT_EXACT, SCROLL_HINT_PSKIP, SCROLL_HINT_SPEC, SCROLL_HINT_MAX_RECTS = 
  SCROLL_SPLICE_ERR_SYNTAX, SCROLL_SPLICE_ERR_REF) = range(6)
 
 
+SCROLL_DYN_PROBE_MAX_QPS = 8
+
+
+class ScrollDynProbe(ctypes.Structure):
+    _fields_ = [("sse", ctypes.c_uint64 * 3), ("bits", ctypes.c_uint32), ("nonzero", ctypes.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} not built: run `make -C h264-scroll-encoder_amd` "
@@ -203,6 +210,12 @@ def _load():
         "scroll_batch_dyn_sse": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                 P(ctypes.c_uint64)]),
         "scroll_batch_dyn_recon_ms": (ctypes.c_float, [ctypes.c_void_p]),
+        "scroll_batch_dyn_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u8p, ctypes.c_int, ctypes.c_void_p]),
+        "scroll_batch_dyn_probe_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                         P(ScrollDynProbe)]),
+        "scroll_batch_dyn_probe_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t),
+                                                            P(ctypes.c_size_t)]),
+        "scroll_batch_dyn_probe_ms": (ctypes.c_float, [ctypes.c_void_p]),
         "scroll_batch_kernel_stats_ex": (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_double),
                                                         P(ctypes.c_int)]),
         "scroll_batch_set_hints": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
@@ -744,11 +757,72 @@ class Batch:
         reconstruction kernels (-1 without)"""
         return lib.scroll_batch_dyn_recon_ms(self.h)
 
+    # ---- probing the rect at candidate QPs ----
+    def dyn_probe(self, nframes, qps, stream=None):
+        """what the next compose(nframes) of the plain dynamic rect would
+        produce at each candidate QP, without committing anything
+        (scroll_batch_dyn_probe): a numpy structured array [S][F][len(qps)]
+        with fields sse (3 x u64: Y, Cb, Cr), bits, nonzero and valid (0: the
+        frame has no dynamic NAL, its other fields are 0)"""
+        import numpy as np
+        q = bytes(int(v) if 0 <= int(v) <= 255 else 255 for v in qps)      # out of range: refused there
+        self._chk(lib.scroll_batch_dyn_probe(self.h, nframes, u8buf(q) if q else None, len(q), stream), "dyn_probe")
+        out = np.zeros((self.num_streams, nframes, len(q)), dtype=_probe_dtype())
+        r = ScrollDynProbe()
+        for s in range(out.shape[0]):
+            for f in range(nframes):
+                for k in range(len(q)):
+                    if self._chk(lib.scroll_batch_dyn_probe_result(self.h, s, f, k, ctypes.byref(r)),
+                                 "dyn_probe_result") == 1:
+                        break
+                    out[s, f, k] = ((r.sse[0], r.sse[1], r.sse[2]), r.bits, r.nonzero, 1)
+        return out
+
+    def dyn_probe_device(self):
+        """(device pointer, stream stride, frame stride) of the last probe's
+        results, ScrollDynProbe [stream][frame][SCROLL_DYN_PROBE_MAX_QPS]"""
+        ls, lf = ctypes.c_size_t(), ctypes.c_size_t()
+        p = lib.scroll_batch_dyn_probe_device(self.h, ctypes.byref(ls), ctypes.byref(lf))
+        return p, ls.value, lf.value
+
+    def dyn_probe_ms(self):
+        """with enable_timing: HIP-event ms of the last probe's launches (-1
+        without)"""
+        return lib.scroll_batch_dyn_probe_ms(self.h)
+
     def last_bytes(self):
         return lib.scroll_batch_last_bytes(self.h)
 
     def last_nals(self):
         return lib.scroll_batch_last_nals(self.h)
+
+
+def _probe_dtype():
+    import numpy as np
+    return np.dtype([("sse", np.uint64, 3), ("bits", np.uint32), ("nonzero", np.uint32), ("valid", np.uint8)])
+
+
+def pick_qp(res, qps, max_bits):
+    """Per (stream, frame) of a dyn_probe result: the candidate QP with the
+    smallest total squared error (Y + Cb + Cr) among those whose bits fit
+    max_bits; equal errors go to the fewer bits, then to the earlier
+    candidate.  -1 where none fits or the frame has no dynamic NAL (valid
+    0).  res: [..., len(qps)]; returns an int32 array of res.shape[:-1]."""
+    import numpy as np
+    res = np.asarray(res)
+    qps = np.asarray(qps, dtype=np.int32)
+    assert res.shape[-1] == qps.shape[0]
+    ok = res["bits"].astype(np.int64) <= int(max_bits)
+    if "valid" in res.dtype.names:
+        ok &= res["valid"] != 0
+    err = res["sse"].astype(np.float64).sum(-1)           # exact below 2^53
+    big = np.finfo(np.float64).max
+    key = np.where(ok, err, big)
+    best = key.min(-1, keepdims=True)
+    tie = ok & (key == best)
+    bits = np.where(tie, res["bits"].astype(np.int64), np.iinfo(np.int64).max)
+    idx = bits.argmin(-1)                                  # the first of the fewest bits
+    return np.where(ok.any(-1), qps[idx], -1).astype(np.int32)
 
 
 def header_symbols():

@@ -304,6 +304,66 @@ uint8_t *scroll_batch_dyn_recon_device(ScrollBatch *b, size_t *stream_stride, si
 int scroll_batch_dyn_recon(ScrollBatch *b, int s, int f, uint8_t *dst);      /* 384*w*h host bytes */
 int scroll_batch_dyn_sse(ScrollBatch *b, int s, int f, uint64_t sse[3]);     /* Y, Cb, Cr */
 float scroll_batch_dyn_recon_ms(ScrollBatch *b);
+
+/* ---- probing the rect at candidate QPs, before the frame is spent ----
+ * Everything above answers after the compose, when the stream has moved on
+ * (frame_num, the waypoint table).  The probe answers before: for the
+ * offsets of scroll_batch_set_offsets and the source of set_dyn_source /
+ * _device / _synth, what the next scroll_batch_compose(b, nframes) of the
+ * plain dynamic rect would produce per frame at each of nq candidate QPs
+ * (every stream gets the same list), whatever QP the streams are set to.
+ * It commits nothing: stream state, arenas, NAL lists, dyn_frame_info, the
+ * reconstruction and the SSE sums of the last compose stay as they are, and
+ * a compose after it emits the bytes it would have emitted without it (the
+ * probe plans and resolves its prediction rows in buffers of its own,
+ * allocated on the first probe, freed by set_dyn_rect and destroy).
+ *
+ * Per frame and candidate QP q (ScrollDynProbe, exact integers):
+ *   sse[3]    what scroll_batch_dyn_sse reports after a compose at q;
+ *   bits      the rect MBs' coded_block_pattern + mb_qp_delta + residual
+ *             bits at q (oracle/dyn_oracle.c or_mb_residual's syntax; nC
+ *             from the left / top TotalCoeffs, MBs outside the rect
+ *             available with 0, picture edges unavailable);
+ *   nonzero   the sum of TotalCoeff over the rect's blocks (luma, chroma DC,
+ *             chroma AC).
+ * From bits to a size: nothing else in the dynamic NAL depends on the QP but
+ * slice_qp_delta, so its RBSP bits before the stop bit are
+ *     bits(q) + len(se(q - 26)) + C(frame),
+ * C one constant per frame (slice header, MB heads, static rows): known from
+ * any one compose or probe-and-compose of that frame, and it cancels when
+ * candidates are compared.  Emulation-prevention bytes come on top.
+ *
+ *   scroll_batch_dyn_probe(b, nframes, qps, nq, hip_stream)   asynchronous on
+ *       hip_stream (0 = the batch's own).  SCROLL_ERR_CONFIG without a
+ *       dynamic rect or references, and with UI hints set (the rect under
+ *       hints is not probed: clear the hints); SCROLL_ERR_ARG for nq outside
+ *       1..SCROLL_DYN_PROBE_MAX_QPS, a QP outside 0..51 or nframes outside
+ *       0..max_frames.  A stream that must keep QP 26 (its config has the
+ *       deblocking filter on) is probed like any other: its numbers at other
+ *       QPs are informational.
+ *   scroll_batch_dyn_probe_result(b, s, f, k, out)   candidate k of frame f of
+ *       stream s of the last probe; synchronises the probe's stream.  0; 1
+ *       when the frame has no dynamic NAL (a waypoint frame in experiment
+ *       mode; nothing written), as scroll_batch_dyn_frame_info;
+ *       SCROLL_ERR_ARG for s, f or k outside the last probe;
+ *       SCROLL_ERR_CONFIG before any probe or after set_dyn_rect dropped it;
+ *       SCROLL_ERR_DEVICE if not every rect row of the frame was counted
+ *       (never 0 over partial sums).
+ *   scroll_batch_dyn_probe_device(b, &ls, &lf)   the device results,
+ *       [stream][frame][SCROLL_DYN_PROBE_MAX_QPS] at byte strides ls / lf;
+ *       NULL before the first probe.  Valid on the probe's stream after it.
+ *   scroll_batch_dyn_probe_ms(b)   with scroll_batch_enable_timing: HIP-event
+ *       ms of the last probe's launches; -1 without. */
+#define SCROLL_DYN_PROBE_MAX_QPS 8
+typedef struct {
+    uint64_t sse[3];    /* Y, Cb, Cr: what scroll_batch_dyn_sse would report at this QP */
+    uint32_t bits;      /* the rect MBs' coded_block_pattern + mb_qp_delta + residual bits */
+    uint32_t nonzero;   /* sum of TotalCoeff over the rect's blocks (luma, chroma DC, chroma AC) */
+} ScrollDynProbe;       /* 32 bytes */
+int scroll_batch_dyn_probe(ScrollBatch *b, int nframes, const uint8_t *qps, int nq, void *hip_stream);
+int scroll_batch_dyn_probe_result(ScrollBatch *b, int s, int f, int k, ScrollDynProbe *out);
+const ScrollDynProbe *scroll_batch_dyn_probe_device(ScrollBatch *b, size_t *stream_stride, size_t *frame_stride);
+float scroll_batch_dyn_probe_ms(ScrollBatch *b);   /* with enable_timing; -1 without */
 /* HIP-event ms of the timed composes since the last call: plan (both
  * passes), emit, dyn stage (= dyn code + dyn pack), dyn emit, dyn code
  * (k_dyn_rows + k_dyn_code), dyn pack (k_dyn_group + k_dyn_ep); accumulators reset
