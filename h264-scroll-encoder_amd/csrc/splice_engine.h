@@ -85,7 +85,7 @@ typedef struct {
  * top MB is in the rect and the same slice.  232 bytes; the first 96 (motion,
  * cbp, TotalCoeffs, TrailingOnes, the intra / residual fields) are what the
  * stage's counting sweep reads; per piece a u16: its body's length in bits
- * (<= 625 with level_prefix <= 15) | the bits of its coeff_token in the
+ * (<= 448 with level_prefix <= 15) | the bits of its coeff_token in the
  * external slice (<= 16) << 11 -- the pieces are contiguous from res_off in
  * syntax order, so the writing sweep finds each body by a running sum (round
  * 6: a u16 length and a u32 offset per piece, 352-byte records); the blocks'

@@ -1269,10 +1269,62 @@ static void ext_header(or_bits *b, const or_cfg *c, const or_ext_params *p, int 
     if (c->deblock) or_ue(b, 1);
 }
 
+/* mb_qp_delta in the standard's range (7.4.5): a jump of +51 is written as -1 */
+static int ext_qpd(int d) { return d > 25 ? d - 52 : (d < -26 ? d + 52 : d); }
+
+/* the residual of one MB from its pieces' coefficients (7.3.5.3): the
+ * Intra16x16DCLevel piece 26 first, luma blocks of 16 coefficients (15 for
+ * an I_16x16's AC), chroma DC, chroma AC; t = the MB's TotalCoeffs */
+static void ext_residual(or_bits *b, int cbp, int i16, int (*coef)[16], uint8_t *t, const uint8_t *L,
+                         const uint8_t *T)
+{
+    if (i16) or_cavlc_block(b, coef[26], 16, sp_piece_nc(0, t, L, T));
+    for (int blk = 0; blk < 16; ++blk) {
+        if (!(cbp & (1 << (blk >> 2)))) continue;
+        const int i = sp_blk_raster(blk);
+        t[i] = (uint8_t)or_cavlc_block(b, coef[i], i16 ? 15 : 16, sp_piece_nc(i, t, L, T));
+    }
+    if (cbp >> 4) {
+        for (int i = 16; i < 18; ++i) or_cavlc_block(b, coef[i], 4, -1);
+        if ((cbp >> 4) == 2)
+            for (int i = 18; i < 26; ++i)
+                t[i] = (uint8_t)or_cavlc_block(b, coef[i], 15, sp_piece_nc(i, t, L, T));
+    }
+}
+
+/* the random coefficients of such a residual, drawn in its coding order; a
+ * scripted MB d brings its own */
+static void ext_coefs(uint32_t *s, const or_ext_params *p, int cbp, int i16, int (*coef)[16], const or_ext_mb *d)
+{
+    if (d) {
+        memcpy(coef, d->coef, sizeof(d->coef));
+        return;
+    }
+    if (i16) sp_rand_block(s, p, coef[26], 16);
+    for (int blk = 0; blk < 16; ++blk)
+        if (cbp & (1 << (blk >> 2))) sp_rand_block(s, p, coef[sp_blk_raster(blk)], i16 ? 15 : 16);
+    if (cbp >> 4) {
+        for (int i = 16; i < 18; ++i) sp_rand_block(s, p, coef[i], 4);
+        if ((cbp >> 4) == 2)
+            for (int i = 18; i < 26; ++i) sp_rand_block(s, p, coef[i], 15);
+    }
+}
+
+/* the next MB QP: the scripted one, or the current one with the jitter */
+static int ext_next_qp(uint32_t *s, const or_ext_params *p, int qp, const or_ext_mb *d)
+{
+    if (d) return d->qp;
+    const int j = p->qp_jitter;
+    const int nq = qp + (j ? (int)(sp_rng(s) % (uint32_t)(2 * j + 1)) - j : 0);
+    return nq < 0 ? 0 : (nq > 51 ? 51 : nq);
+}
+
 /* an intra MB of the stand-in encoder (type 1 I_4x4, 2 I_16x16, 3 I_PCM, or
- * mbt_force 5..30), its modes predicted as the parse does (8.3.1.1) */
+ * mbt_force 5..30), its modes predicted as the parse does (8.3.1.1); every
+ * value drawn from s, or taken from the scripted MB d */
 static void ext_intra(or_bits *b, uint32_t *s, const or_ext_params *p, int type, int mbt_force, int x, int y,
-                      int W, const int *sid, int8_t (*im)[16], uint8_t (*tcs)[OR_SPLICE_PIECES], int *qp)
+                      int W, const int *sid, int8_t (*im)[16], uint8_t (*tcs)[OR_SPLICE_PIECES], int *qp,
+                      const or_ext_mb *d)
 {
     const int m = y * W + x, u = sid[m];
     const uint8_t *L = x && sid[m - 1] == u ? tcs[m - 1] : NULL, *T = y && sid[m - W] == u ? tcs[m - W] : NULL;
@@ -1284,11 +1336,11 @@ static void ext_intra(or_bits *b, uint32_t *s, const or_ext_params *p, int type,
     if (type == 3) {
         or_ue(b, 30 - mo);
         while (b->nbits & 7) or_put(b, 0, 1);
-        for (int k = 0; k < 384; ++k) or_put(b, p->pcm_zero ? 0u : (sp_rng(s) & 255u), 8);
+        for (int k = 0; k < 384; ++k) or_put(b, d ? d->pcm[k] : (p->pcm_zero ? 0u : (sp_rng(s) & 255u)), 8);
         memset(t, 16, OR_SPLICE_PIECES);
         return;
     }
-    int coef[16];
+    int coef[OR_SPLICE_PIECES][16];
     if (type == 1) {
         or_ue(b, 5 - mo);
         for (int blk = 0; blk < 16; ++blk) {
@@ -1300,7 +1352,7 @@ static void ext_intra(or_bits *b, uint32_t *s, const or_ext_params *p, int type,
             else if (y && sid[m - W] == u) mB = im[m - W][ri + 12];
             const int a = mA < 0 ? 2 : mA, bb = mB < 0 ? 2 : mB;
             const int pm = (mA == -2 || mB == -2) ? 2 : (a < bb ? a : bb);
-            const int md = (sp_rng(s) % 3 == 0) ? pm : (int)(sp_rng(s) % 9);
+            const int md = d ? d->imode[ri] : ((sp_rng(s) % 3 == 0) ? pm : (int)(sp_rng(s) % 9));
             if (md == pm) {
                 or_put(b, 1, 1);
             } else {
@@ -1309,65 +1361,30 @@ static void ext_intra(or_bits *b, uint32_t *s, const or_ext_params *p, int type,
             }
             im[m][ri] = (int8_t)md;
         }
-        or_ue(b, sp_rng(s) % 4);                                  /* intra_chroma_pred_mode */
-        const int cbp = (int)(sp_rng(s) % 48);
+        or_ue(b, d ? (uint32_t)d->cmode : sp_rng(s) % 4);         /* intra_chroma_pred_mode */
+        const int cbp = d ? d->cbp : (int)(sp_rng(s) % 48);
         int code = 0;
         while (SP_CBP_INTRA[code] != cbp) ++code;
         or_ue(b, (uint32_t)code);
         if (!cbp) return;
-        const int j = p->qp_jitter;
-        int nq = *qp + (j ? (int)(sp_rng(s) % (uint32_t)(2 * j + 1)) - j : 0);
-        nq = nq < 0 ? 0 : (nq > 51 ? 51 : nq);
-        or_se(b, nq - *qp);
+        const int nq = ext_next_qp(s, p, *qp, d);
+        or_se(b, ext_qpd(nq - *qp));
         *qp = nq;
-        for (int blk = 0; blk < 16; ++blk) {
-            if (!(cbp & (1 << (blk >> 2)))) continue;
-            const int i = sp_blk_raster(blk);
-            sp_rand_block(s, p, coef, 16);
-            t[i] = (uint8_t)or_cavlc_block(b, coef, 16, sp_piece_nc(i, t, L, T));
-        }
-        if (cbp >> 4) {
-            for (int i = 16; i < 18; ++i) {
-                sp_rand_block(s, p, coef, 4);
-                or_cavlc_block(b, coef, 4, -1);
-            }
-            if ((cbp >> 4) == 2)
-                for (int i = 18; i < 26; ++i) {
-                    sp_rand_block(s, p, coef, 15);
-                    t[i] = (uint8_t)or_cavlc_block(b, coef, 15, sp_piece_nc(i, t, L, T));
-                }
-        }
+        ext_coefs(s, p, cbp, 0, coef, d);
+        ext_residual(b, cbp, 0, coef, t, L, T);
         return;
     }
     /* I_16x16: prediction mode, chroma cbp, luma cbp in the mb_type */
-    const int it = mbt_force ? mbt_force - 6 : (int)(sp_rng(s) % 24);
+    const int it = mbt_force ? mbt_force - 6
+                             : (d ? d->imode[0] + 4 * (d->cbp >> 4) + (d->cbp & 15 ? 12 : 0) : (int)(sp_rng(s) % 24));
     const int cbl = it >= 12 ? 15 : 0, cbc = (it >> 2) % 3;
     or_ue(b, (uint32_t)(6 + it) - mo);
-    or_ue(b, sp_rng(s) % 4);                                      /* intra_chroma_pred_mode */
-    const int j = p->qp_jitter;
-    int nq = *qp + (j ? (int)(sp_rng(s) % (uint32_t)(2 * j + 1)) - j : 0);
-    nq = nq < 0 ? 0 : (nq > 51 ? 51 : nq);
-    or_se(b, nq - *qp);                                           /* mb_qp_delta: always */
+    or_ue(b, d ? (uint32_t)d->cmode : sp_rng(s) % 4);             /* intra_chroma_pred_mode */
+    const int nq = ext_next_qp(s, p, *qp, d);
+    or_se(b, ext_qpd(nq - *qp));                                  /* mb_qp_delta: always */
     *qp = nq;
-    sp_rand_block(s, p, coef, 16);                                /* Intra16x16DCLevel */
-    or_cavlc_block(b, coef, 16, sp_piece_nc(0, t, L, T));
-    if (cbl)
-        for (int blk = 0; blk < 16; ++blk) {                      /* Intra16x16ACLevel */
-            const int i = sp_blk_raster(blk);
-            sp_rand_block(s, p, coef, 15);
-            t[i] = (uint8_t)or_cavlc_block(b, coef, 15, sp_piece_nc(i, t, L, T));
-        }
-    if (cbc) {
-        for (int i = 16; i < 18; ++i) {
-            sp_rand_block(s, p, coef, 4);
-            or_cavlc_block(b, coef, 4, -1);
-        }
-        if (cbc == 2)
-            for (int i = 18; i < 26; ++i) {
-                sp_rand_block(s, p, coef, 15);
-                t[i] = (uint8_t)or_cavlc_block(b, coef, 15, sp_piece_nc(i, t, L, T));
-            }
-    }
+    ext_coefs(s, p, cbl | cbc << 4, 1, coef, d);
+    ext_residual(b, cbl | cbc << 4, 1, coef, t, L, T);
 }
 
 /* the stand-in encoder's NAL header: IDR pictures are nal_unit_type 5, a
@@ -1375,8 +1392,51 @@ static void ext_intra(or_bits *b, uint32_t *s, const or_ext_params *p, int type,
 static int ext_nut(const or_ext_params *p) { return p->islice == 2 ? 5 : 1; }
 static int ext_ref_idc(const or_ext_params *p) { return p->islice == 2 && !p->ref_idc ? 3 : p->ref_idc; }
 
-size_t or_ext_slice(uint8_t *dst, size_t cap, const or_cfg *c, int W, int H, uint32_t seed,
-                    const or_ext_params *p)
+/* one inter MB (7.3.5 / 7.3.5.1-2): mb_type mbt (0 P_L0_16x16, 1 16x8, 2 8x16,
+ * 3 P_8x8, 4 P_8x8ref0), sub_mb_types, ref_idx per partition and the mvd of
+ * every (sub-)partition's motion (vx, vy in decoding order) against 8.4.1.3;
+ * fills the field */
+static void ext_inter(or_bits *b, const sp_field *F, int x, int y, int nrefs, int mbt, int sub, const int *refs,
+                      const int *vx, const int *vy)
+{
+    or_ue(b, (uint32_t)mbt);
+    if (mbt == 0) {
+        or_mvi A, B, C, Cr, D;
+        sp_nb16(F, x, y, &A, &B, &C, &Cr, &D);
+        int px, py;
+        or_spec_predict(&A, &B, &C, refs[0], &px, &py);
+        if (nrefs == 2) or_put(b, (uint32_t)(1 - refs[0]), 1);
+        else if (nrefs > 2) or_ue(b, (uint32_t)refs[0]);
+        or_se(b, vx[0] - px);
+        or_se(b, vy[0] - py);
+        for (int k = 0; k < 16; ++k) *sp_at(F, x, y, k & 3, k >> 2) = (or_mvi){vx[0], vy[0], refs[0], 1};
+        return;
+    }
+    const int part = mbt == 4 ? 3 : mbt;
+    if (part == 3)
+        for (int i = 0; i < 4; ++i) or_ue(b, (uint32_t)((sub >> (2 * i)) & 3));
+    const int nref = part == 3 ? 4 : 2;
+    for (int i = 0; i < nref && mbt != 4; ++i) {
+        if (nrefs == 2) or_put(b, (uint32_t)(1 - refs[i]), 1);
+        else if (nrefs > 2) or_ue(b, (uint32_t)refs[i]);
+    }
+    sp_part ps[16];
+    const int np = sp_partitions(part, sub, ps);
+    unsigned done = 0;
+    for (int k = 0; k < np; ++k) {
+        const int rf = refs[ps[k].mb_part];
+        int px, py;
+        sp_mvp(F, x, y, done, part, &ps[k], rf, &px, &py);
+        or_se(b, vx[k] - px);
+        or_se(b, vy[k] - py);
+        sp_fill(F, x, y, &ps[k], (or_mvi){vx[k], vy[k], rf, 1}, &done);
+    }
+}
+
+/* the stand-in encoder: MBs drawn from the seed, or (script) the MBs given,
+ * with a new slice at each MB of first[0..nfirst) */
+static size_t ext_picture(uint8_t *dst, size_t cap, const or_cfg *c, int W, int H, uint32_t seed,
+                          const or_ext_params *p, const or_ext_mb *script, const int *first, int nfirst)
 {
     uint32_t s = seed * 2654435761u + 0x9E3779B9u;
     if (!s) s = 1;
@@ -1393,11 +1453,14 @@ size_t or_ext_slice(uint8_t *dst, size_t cap, const or_cfg *c, int W, int H, uin
     sp_field F = {W, (or_mvi *)calloc((size_t)nmb * 16, sizeof(or_mvi)), sid, 0};
     uint8_t(*tcs)[OR_SPLICE_PIECES] = calloc((size_t)nmb, OR_SPLICE_PIECES);
     size_t nb = 0;
-    int run = 0;
+    int run = 0, nextf = 0;
     const int rg = p->mv_range;
     for (int m = 0; m < nmb; ++m) {
         const int x = m % W, y = m / W;
-        if (p->slice_rows > 0 && x == 0 && y > 0 && y % p->slice_rows == 0) {
+        const or_ext_mb *d = script ? &script[m] : NULL;
+        int brk = !script && p->slice_rows > 0 && x == 0 && y > 0 && y % p->slice_rows == 0;
+        while (script && nextf < nfirst && first[nextf] <= m) brk |= first[nextf++] == m && m > 0;
+        if (brk) {
             /* the next slice: this one ends (pending skips, trailing bits) */
             if (run > 0) or_ue(&b, (uint32_t)run);
             run = 0;
@@ -1413,15 +1476,22 @@ size_t or_ext_slice(uint8_t *dst, size_t cap, const or_cfg *c, int W, int H, uin
         memset(im[m], -1, 16);
         or_mvi A, B, C, Cr, D;
         sp_nb16(&F, x, y, &A, &B, &C, &Cr, &D);
-        if (m == p->bad_mb && (p->bad_type < 5 || p->bad_type > 30)) {
+        if (d && d->kind >= OR_EXT_I4X4) {                        /* a scripted intra MB */
+            if (!p->islice) or_ue(&b, (uint32_t)run);
+            run = 0;
+            ext_intra(&b, &s, p, d->kind - OR_EXT_I4X4 + 1, 0, x, y, W, sid, im, tcs, &qp, d);
+            for (int q = 0; q < 16; ++q) *sp_at(&F, x, y, q & 3, q >> 2) = (or_mvi){0, 0, -1, 1};
+            continue;
+        }
+        if (!d && m == p->bad_mb && (p->bad_type < 5 || p->bad_type > 30)) {
             or_ue(&b, (uint32_t)run);
             or_ue(&b, (uint32_t)p->bad_type);
             or_put(&b, sp_rng(&s), 32);
             run = 0;
             break;
         }
-        const int forced = m == p->bad_mb ? p->bad_type : 0;     /* a valid intra MB of that type here */
-        if (p->islice) {                                          /* every MB intra, no mb_skip_run */
+        const int forced = !d && m == p->bad_mb ? p->bad_type : 0; /* a valid intra MB of that type here */
+        if (!d && p->islice) {                                    /* every MB intra, no mb_skip_run */
             const int interior = x > 0 && x < W - 1 && y > top;
             const int k = (int)(sp_rng(&s) % 5);
             const int ty = p->intra_types ? p->intra_types : 7;
@@ -1430,11 +1500,11 @@ size_t or_ext_slice(uint8_t *dst, size_t cap, const or_cfg *c, int W, int H, uin
                 type = k < 2 ? 1 : (k < 4 ? 2 : 3);
                 if (!(ty >> (type - 1) & 1)) type = (ty & 2) ? 2 : ((ty & 1) ? 1 : 3);
             }
-            ext_intra(&b, &s, p, type, forced, x, y, W, sid, im, tcs, &qp);
+            ext_intra(&b, &s, p, type, forced, x, y, W, sid, im, tcs, &qp, NULL);
             for (int q = 0; q < 16; ++q) *sp_at(&F, x, y, q & 3, q >> 2) = (or_mvi){0, 0, -1, 1};
             continue;
         }
-        if (!forced && (int)(sp_rng(&s) % 1000) < p->skip_pm) {
+        if (d ? d->kind == OR_EXT_SKIP : (!forced && (int)(sp_rng(&s) % 1000) < p->skip_pm)) {
             int px, py;
             sp_pskip(&A, &B, &C, &px, &py);
             for (int k = 0; k < 16; ++k) *sp_at(&F, x, y, k & 3, k >> 2) = (or_mvi){px, py, 0, 1};
@@ -1443,7 +1513,7 @@ size_t or_ext_slice(uint8_t *dst, size_t cap, const or_cfg *c, int W, int H, uin
             continue;
         }
         /* intra where any rect placement splices it (splice_oracle.h) */
-        if (forced || (p->intra_pm > 0 && (int)(sp_rng(&s) % 1000) < p->intra_pm)) {
+        if (!d && (forced || (p->intra_pm > 0 && (int)(sp_rng(&s) % 1000) < p->intra_pm))) {
             const int interior = x > 0 && x < W - 1 && y > top;
             const int k = (int)(sp_rng(&s) % 5);
             int type = !interior ? 3 : (k < 2 ? 1 : (k < 4 ? 2 : 3));
@@ -1454,92 +1524,67 @@ size_t or_ext_slice(uint8_t *dst, size_t cap, const or_cfg *c, int W, int H, uin
             }
             or_ue(&b, (uint32_t)run);
             run = 0;
-            ext_intra(&b, &s, p, type, forced, x, y, W, sid, im, tcs, &qp);
+            ext_intra(&b, &s, p, type, forced, x, y, W, sid, im, tcs, &qp, NULL);
             for (int q = 0; q < 16; ++q) *sp_at(&F, x, y, q & 3, q >> 2) = (or_mvi){0, 0, -1, 1};
             continue;
         }
     inter:;
-        int ref = (int)(sp_rng(&s) % (uint32_t)(p->max_ref + 1));
-        if (ref >= nrefs) ref = nrefs - 1;
-        const int mx = rg ? (int)(sp_rng(&s) % (uint32_t)(2 * rg + 1)) - rg : 0;
-        const int my = rg ? (int)(sp_rng(&s) % (uint32_t)(2 * rg + 1)) - rg : 0;
-        /* a partitioned MB (drawn only when part_pm > 0: the other
-         * parameters keep their slices bit for bit) */
-        int mbt = 0;
-        if (p->part_pm > 0 && (int)(sp_rng(&s) % 1000) < p->part_pm) mbt = 1 + (int)(sp_rng(&s) % 4);
-        const int cbp = (int)(sp_rng(&s) % 1000) < p->cbp_pm ? 1 + (int)(sp_rng(&s) % 47) : 0;
-        or_ue(&b, (uint32_t)run);
-        run = 0;
-        or_ue(&b, (uint32_t)mbt);
-        if (mbt == 0) {
-            int px, py;
-            or_spec_predict(&A, &B, &C, ref, &px, &py);
-            if (nrefs == 2) or_put(&b, (uint32_t)(1 - ref), 1);
-            else if (nrefs > 2) or_ue(&b, (uint32_t)ref);
-            or_se(&b, mx - px);
-            or_se(&b, my - py);
-            for (int k = 0; k < 16; ++k) *sp_at(&F, x, y, k & 3, k >> 2) = (or_mvi){mx, my, ref, 1};
-        } else {
-            const int part = mbt == 4 ? 3 : mbt;
-            int sub = 0, refs[4] = {ref, ref, ref, ref};
-            if (part == 3)
-                for (int i = 0; i < 4; ++i) {
-                    const int st = (int)(sp_rng(&s) % 4);
-                    sub |= st << (2 * i);
-                    or_ue(&b, (uint32_t)st);
-                }
-            const int nref = part == 3 ? 4 : 2;
-            for (int i = 0; i < nref; ++i) {
-                refs[i] = mbt == 4 ? 0 : (int)(sp_rng(&s) % (uint32_t)(p->max_ref + 1));
-                if (refs[i] >= nrefs) refs[i] = nrefs - 1;
-                if (mbt == 4) continue;
-                if (nrefs == 2) or_put(&b, (uint32_t)(1 - refs[i]), 1);
-                else if (nrefs > 2) or_ue(&b, (uint32_t)refs[i]);
+        int mbt, cbp, sub = 0, refs[4], vx[16], vy[16];
+        if (d) {
+            mbt = d->kind - OR_EXT_16X16;
+            cbp = d->cbp;
+            for (int i = 0; i < 4; ++i) {
+                sub |= (d->sub[i] & 3) << (2 * i);
+                refs[i] = mbt == 4 ? 0 : d->ref[i];
             }
-            sp_part ps[16];
-            const int np = sp_partitions(part, sub, ps);
-            unsigned done = 0;
-            for (int k = 0; k < np; ++k) {
-                /* motion near the MB's own draw, so predictions and mvds vary */
-                const int vx = mx + (rg ? (int)(sp_rng(&s) % 17) - 8 : 0);
-                const int vy = my + (rg ? (int)(sp_rng(&s) % 17) - 8 : 0);
-                const int rf = refs[ps[k].mb_part];
-                int px, py;
-                sp_mvp(&F, x, y, done, part, &ps[k], rf, &px, &py);
-                or_se(&b, vx - px);
-                or_se(&b, vy - py);
-                sp_fill(&F, x, y, &ps[k], (or_mvi){vx, vy, rf, 1}, &done);
+            memcpy(vx, d->mvx, sizeof(vx));
+            memcpy(vy, d->mvy, sizeof(vy));
+        } else {
+            int ref = (int)(sp_rng(&s) % (uint32_t)(p->max_ref + 1));
+            if (ref >= nrefs) ref = nrefs - 1;
+            const int mx = rg ? (int)(sp_rng(&s) % (uint32_t)(2 * rg + 1)) - rg : 0;
+            const int my = rg ? (int)(sp_rng(&s) % (uint32_t)(2 * rg + 1)) - rg : 0;
+            /* a partitioned MB (drawn only when part_pm > 0: the other
+             * parameters keep their slices bit for bit) */
+            mbt = 0;
+            if (p->part_pm > 0 && (int)(sp_rng(&s) % 1000) < p->part_pm) mbt = 1 + (int)(sp_rng(&s) % 4);
+            cbp = (int)(sp_rng(&s) % 1000) < p->cbp_pm ? 1 + (int)(sp_rng(&s) % 47) : 0;
+            refs[0] = refs[1] = refs[2] = refs[3] = ref;
+            vx[0] = mx;
+            vy[0] = my;
+            if (mbt) {
+                const int part = mbt == 4 ? 3 : mbt;
+                if (part == 3)
+                    for (int i = 0; i < 4; ++i) sub |= (int)(sp_rng(&s) % 4) << (2 * i);
+                const int nref = part == 3 ? 4 : 2;
+                for (int i = 0; i < nref; ++i) {
+                    refs[i] = mbt == 4 ? 0 : (int)(sp_rng(&s) % (uint32_t)(p->max_ref + 1));
+                    if (refs[i] >= nrefs) refs[i] = nrefs - 1;
+                }
+                sp_part ps[16];
+                const int np = sp_partitions(part, sub, ps);
+                for (int k = 0; k < np; ++k) {
+                    /* motion near the MB's own draw, so predictions and mvds vary */
+                    vx[k] = mx + (rg ? (int)(sp_rng(&s) % 17) - 8 : 0);
+                    vy[k] = my + (rg ? (int)(sp_rng(&s) % 17) - 8 : 0);
+                }
             }
         }
+        or_ue(&b, (uint32_t)run);
+        run = 0;
+        ext_inter(&b, &F, x, y, nrefs, mbt, sub, refs, vx, vy);
         or_ue(&b, (uint32_t)or_cbp_code(cbp));
         uint8_t *t = tcs[m];
         memset(t, 0, OR_SPLICE_PIECES);
         if (cbp) {
-            const int j = p->qp_jitter;
-            int nq = qp + (j ? (int)(sp_rng(&s) % (uint32_t)(2 * j + 1)) - j : 0);
-            nq = nq < 0 ? 0 : (nq > 51 ? 51 : nq);
-            or_se(&b, nq - qp);
+            const int nq = ext_next_qp(&s, p, qp, d);
+            or_se(&b, ext_qpd(nq - qp));
             qp = nq;
             const uint8_t *L = x && sid[m - 1] == slice ? tcs[m - 1] : NULL;
             const uint8_t *T = y && sid[m - W] == slice ? tcs[m - W] : NULL;
-            int coef[16];
-            for (int blk = 0; blk < 16; ++blk) {
-                if (!(cbp & (1 << (blk >> 2)))) continue;
-                const int i = sp_blk_raster(blk);
-                sp_rand_block(&s, p, coef, 16);
-                t[i] = (uint8_t)or_cavlc_block(&b, coef, 16, sp_piece_nc(i, t, L, T));
-            }
-            if (cbp >> 4) {
-                for (int i = 16; i < 18; ++i) {
-                    sp_rand_block(&s, p, coef, 4);
-                    or_cavlc_block(&b, coef, 4, -1);
-                }
-                if ((cbp >> 4) == 2)
-                    for (int i = 18; i < 26; ++i) {
-                        sp_rand_block(&s, p, coef, 15);
-                        t[i] = (uint8_t)or_cavlc_block(&b, coef, 15, sp_piece_nc(i, t, L, T));
-                    }
-            }
+            int coef[OR_SPLICE_PIECES][16];
+            ext_coefs(&s, p, cbp, 0, coef, d);
+            ext_residual(&b, cbp, 0, coef, t, L, T);
         }
     }
     if (run > 0) or_ue(&b, (uint32_t)run);
@@ -1551,4 +1596,16 @@ size_t or_ext_slice(uint8_t *dst, size_t cap, const or_cfg *c, int W, int H, uin
     free(sid);
     free(im);
     return nb;
+}
+
+size_t or_ext_slice(uint8_t *dst, size_t cap, const or_cfg *c, int W, int H, uint32_t seed,
+                    const or_ext_params *p)
+{
+    return ext_picture(dst, cap, c, W, H, seed, p, NULL, NULL, 0);
+}
+
+size_t or_ext_slice_script(uint8_t *dst, size_t cap, const or_cfg *c, int W, int H, const or_ext_params *p,
+                           const or_ext_mb *mbs, const int *first, int nfirst)
+{
+    return ext_picture(dst, cap, c, W, H, 1, p, mbs, first, nfirst);
 }

@@ -212,6 +212,37 @@ typedef struct {
 size_t or_ext_slice(uint8_t *dst, size_t cap, const or_cfg *c, int w, int h, uint32_t seed,
                     const or_ext_params *p);
 
+/* ---- the same writer from an explicit description (tests/splicedesign.py):
+ * one or_ext_mb per MB of the w x h picture, nothing drawn.  The header
+ * fields of p hold (nrefs, slice_qp_delta, ref_idc, list_mod, islice); a new
+ * slice starts at each MB of first[0..nfirst) (ascending; MB 0 is implied).
+ * mb_qp_delta is written in the standard's range: QP 0 -> 51 as -1. ---- */
+enum {
+    OR_EXT_SKIP = 0,             /* P_Skip: its motion is the standard's (8.4.1.1)       */
+    OR_EXT_16X16,                /* ref[0], (mvx[0], mvy[0])                             */
+    OR_EXT_16X8,                 /* ref[0..1], mv[0..1]                                  */
+    OR_EXT_8X16,
+    OR_EXT_8X8,                  /* sub[0..3], ref[0..3], mv per sub-partition in decoding order */
+    OR_EXT_8X8REF0,
+    OR_EXT_I4X4,                 /* imode[raster block] = Intra4x4PredMode, cmode, cbp   */
+    OR_EXT_I16X16,               /* imode[0] = its prediction mode, cmode, cbp 0 / 15 | chroma << 4 */
+    OR_EXT_IPCM                  /* pcm[384]                                             */
+};
+typedef struct {
+    int kind;
+    int sub[4], ref[4];
+    int mvx[16], mvy[16];        /* quarter pels, composed-picture displacements          */
+    int cbp;
+    int qp;                      /* the MB's QP where it carries mb_qp_delta              */
+    int imode[16], cmode;
+    int coef[OR_SPLICE_PIECES][16];  /* per piece in scan order: luma raster 0..15 (I_16x16: its
+                                  * 15 AC levels from index 0), 16-17 chroma DC, 18-25 chroma AC,
+                                  * 26 Intra16x16DCLevel                                   */
+    uint8_t pcm[384];
+} or_ext_mb;
+size_t or_ext_slice_script(uint8_t *dst, size_t cap, const or_cfg *c, int w, int h, const or_ext_params *p,
+                           const or_ext_mb *mbs, const int *first, int nfirst);
+
 #ifdef __cplusplus
 }
 #endif

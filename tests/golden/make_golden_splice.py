@@ -131,6 +131,33 @@ def cases(oracle):
                    nrefs=H["nrefs"], ext_sha256=hashlib.sha256(ext).hexdigest(),
                    sha256=hashlib.sha256(nal).hexdigest(), nal_bytes=len(nal), mb_start_bit=b.p,
                    stop_bit=_stop_bit(rbsp)), nal, rbsp
+    # the designed corpus (tests/splicedesign.py reference_pics): the table
+    # walk, the longest MBs and the QP chain as 20x20-MB external slices in
+    # one-slice form, and the NALs composed from their 12x8 forms
+    import splicedesign as sd
+    ext_pics, comp_pics = sd.reference_pics()
+    for name, pic in ext_pics:
+        nal = pic.nal(oracle, "one")
+        H, b, rbsp = hp.slice_header(nal, nrefs_default=2)
+        yield dict(kind="external", case="designed-" + name, nrefs=H["nrefs"],
+                   sha256=hashlib.sha256(nal).hexdigest(), nal_bytes=len(nal), mb_start_bit=b.p,
+                   stop_bit=_stop_bit(rbsp)), nal, rbsp
+    cd = OrCfg()
+    oracle.or_cfg_init(ctypes.byref(cd), w, h)
+    cd.frame_num = 2
+    for k, (name, pic) in enumerate(comp_pics):
+        ext = pic.nal(oracle, "one")
+        rect = (pic.at[0], pic.at[1], pic.W, pic.H)
+        sp = splice_of(*rect, ext)
+        n = oracle.or_splice_scroll_nal(buf, len(buf), ctypes.byref(cd), 40 + k, None, 0, k % 2,
+                                        ctypes.byref(sp), ctypes.byref(err))
+        assert err.value == 0 and n > 0
+        nal = bytes(buf[:n])
+        H, b, rbsp = hp.slice_header(nal)
+        yield dict(kind="composed", case="designed-" + name, off=40 + k, mode=k % 2, rect=list(rect),
+                   nrefs=H["nrefs"], ext_sha256=hashlib.sha256(ext).hexdigest(),
+                   sha256=hashlib.sha256(nal).hexdigest(), nal_bytes=len(nal), mb_start_bit=b.p,
+                   stop_bit=_stop_bit(rbsp)), nal, rbsp
 
 
 def main():
