@@ -1,7 +1,8 @@
 /*
  * hint_device.h -- motion of a hinted / spliced frame, shared by k_hint_stage
  * (hint_kernels.hip), k_splice_stage (splice_kernels.hip), k_hdyn_code
- * (hdyn_kernels.hip) and k_hdyn_recon (hrecon_kernels.hip): the MV field
+ * (hdyn_kernels.hip), k_hdyn_recon (hrecon_kernels.hip) and k_hprobe_class /
+ * k_hdyn_probe (hprobe_kernels.hip): the MV field
  * of the UI hints over the scroll layout, the reference's predictor
  * (h264_writer.c:369-432), the standard's (H.264 8.4.1.3) and P_Skip motion
  * (8.4.1.1).  Bits: oracle/hint_oracle.c.
@@ -49,6 +50,22 @@ __device__ inline Mv field(const ScrollHintRect *rc, const int32_t *wv, int nr, 
     }
     bad = false;
     return y < lay.a_end ? Mv{lay.ra, 0, lay.mva4} : Mv{lay.rb, 0, lay.mvb4};
+}
+
+/* does an MB of this thread's share (MBs t, t + nt, ... of the mbw-wide
+ * picture's nmb) take a rect that names a reference the frame lacks?  Only
+ * the rects' references matter: the motion, and with it the scroll layout
+ * under the rects, is not looked at (k_hint_fb, k_hprobe_class) */
+__device__ inline bool bad_ref_share(const ScrollHintRect *rc, const int32_t *wv, int nr, int mbw, int nmb,
+                                     int nwp, int t, int nt)
+{
+    bool my = false;
+    for (int m = t; m < nmb; m += nt) {
+        bool b1;
+        (void)field(rc, wv, nr, m % mbw, m / mbw, Layout{}, nwp, b1);
+        my |= b1;
+    }
+    return my;
 }
 
 /* get_mv_prediction (h264_writer.c:369-432): C is above-right, else

@@ -281,15 +281,7 @@ __global__ __launch_bounds__(DT) void k_hint_fb(const DevStream *__restrict__ st
         const DevStream *S = st + s;
         const int nwp = nal[(size_t)s * ld_nal + j].nwp;
         const int mbw = S->w / 16, nmb = mbw * (S->h / 16);
-        bool my = false;
-        for (int m = t; m < nmb; m += DT) {
-            bool b1;
-            /* only the rects' references matter: the motion, and with it the
-             * scroll layout under the rects, is not looked at */
-            (void)field(rc, wv, nr, m % mbw, m / mbw, Layout{}, nwp, b1);
-            my |= b1;
-        }
-        if (my) any = 1;
+        if (bad_ref_share(rc, wv, nr, mbw, nmb, nwp, t, DT)) any = 1;
         __syncthreads();
         bad = any != 0;
     }

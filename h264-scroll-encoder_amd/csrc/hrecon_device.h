@@ -33,6 +33,13 @@ using dyn::RefPics;
 using dyn::WpTab;
 using recon::Pics;
 
+/* a rect MB's resolved motion, as the kernels keep it in LDS (k_hdyn_recon,
+ * k_hdyn_probe): pixels (|mv| <= SCROLL_HINT_MAX_MV, the picture's height) */
+constexpr int HR_BAD = 1, HR_GEN = 2;
+struct HrMb {
+    int16_t ref, fl, mvx, mvy;          /* fl: HR_BAD its hint names no valid reference, HR_GEN chroma_needs_gen */
+};
+
 /* bytes X .. X + n - 1 (n <= 5) of a row from the aligned dwords that hold
  * them: needs 0 <= X and X + n <= the row's length.  The second dword is
  * loaded only when one of the n bytes lies in it, so no load leaves the

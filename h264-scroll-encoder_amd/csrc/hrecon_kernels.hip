@@ -41,12 +41,6 @@ using namespace scroll::hrecon;
 namespace {
 
 constexpr int HR_T = 256, HR_NW = HR_T / 64;
-constexpr int HR_BAD = 1, HR_GEN = 2;
-
-struct HrMb {
-    int16_t ref, fl, mvx, mvy;          /* motion in pixels (|mv| <= SCROLL_HINT_MAX_MV, the picture's height) */
-};
-
 struct HreconLds {
     ScrollHintRect rc[SCROLL_HINT_MAX_RECTS];
     int32_t wo[8], wv[8];

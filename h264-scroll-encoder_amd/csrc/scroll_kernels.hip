@@ -24,6 +24,7 @@
 #include "recon_engine.h"
 #include "hrecon_engine.h"
 #include "probe_engine.h"
+#include "hprobe_engine.h"
 #include "hint_engine.h"
 #include "splice_engine.h"
 #include "hdyn_engine.h"
@@ -949,6 +950,8 @@ struct ScrollBatch {
         uint32_t *rows = nullptr, *ctr = nullptr, *done = nullptr;
         uint4 *heads = nullptr;
         ScrollDynProbe *res = nullptr;  /* [max_streams * max_frames][SCROLL_DYN_PROBE_MAX_QPS] */
+        uint8_t *cls = nullptr;         /* [max_streams * max_frames]: k_hprobe_class (scroll_batch_dyn_probe_hinted) */
+        int hinted = 0;                 /* the last probe was the hinted one */
         int nframes = -1, nstreams = 0, nq = 0;   /* the last probe; nframes -1: none */
         hipEvent_t fin = nullptr;       /* recorded after the last probe's launches */
         hipEvent_t ev[2] = {};          /* timing: around them (created on first use) */
@@ -2002,6 +2005,7 @@ static void probe_release(ScrollBatch *b)
     (void)hipFree(p.done);
     (void)hipFree(p.heads);
     (void)hipFree(p.res);
+    (void)hipFree(p.cls);
     p = ScrollBatch::Probe{};
 }
 
@@ -2580,6 +2584,7 @@ int scroll_batch_dyn_probe(ScrollBatch *b, int nframes, const uint8_t *qps, int 
     p.nstreams = S;
     p.nq = nq;
     p.timed = 0;
+    p.hinted = 0;
     if (S > 0 && nframes > 0) {
         const bool timed = b->timing != 0;
         if (timed && !p.ev[0]) {
@@ -2614,6 +2619,98 @@ int scroll_batch_dyn_probe(ScrollBatch *b, int nframes, const uint8_t *qps, int 
     return SCROLL_OK;
 }
 
+/* The same question for the rect under UI hints: what the next compose's
+ * k_hdyn_code would make of every frame (its hint rects, its own rect
+ * position, the fallback), at candidate QPs instead of the frames' own.  The
+ * uploads are the ones that compose would do anyway; the plan goes into the
+ * probe's own NalDesc / DynFrame / PlanPending and the frames' classes into
+ * a buffer of the probe's own, so that nothing of the batch's state, of the
+ * last compose's results or of its fallback flags changes. */
+int scroll_batch_dyn_probe_hinted(ScrollBatch *b, int nframes, const uint8_t *qps, int nq, void *hip_stream)
+{
+    if (!b || !qps || nq < 1 || nq > SCROLL_DYN_PROBE_MAX_QPS) {
+        set_err("scroll_batch_dyn_probe_hinted: 1..%d candidate QPs", SCROLL_DYN_PROBE_MAX_QPS);
+        return SCROLL_ERR_ARG;
+    }
+    if (nframes < 0 || nframes > b->max_frames) {
+        set_err("scroll_batch_dyn_probe_hinted: nframes %d out of range", nframes);
+        return SCROLL_ERR_ARG;
+    }
+    ProbeQps Q{};
+    Q.n = nq;
+    for (int k = 0; k < nq; ++k) {
+        if (qps[k] > 51) {
+            set_err("scroll_batch_dyn_probe_hinted: candidate %d: QP %d outside 0..51", k, qps[k]);
+            return SCROLL_ERR_ARG;
+        }
+        Q.qp[k] = qps[k];
+    }
+    if (!b->dyn_on || !b->dyn_refs) {
+        set_err("scroll_batch_dyn_probe_hinted: needs a dynamic rect with reference pictures "
+                "(scroll_batch_set_dyn_rect, scroll_batch_set_dyn_refs)");
+        return SCROLL_ERR_CONFIG;
+    }
+    if (!b->hint_on) {
+        set_err("scroll_batch_dyn_probe_hinted: covers the rect under UI hints (scroll_batch_set_hints); "
+                "the plain dynamic rect is scroll_batch_dyn_probe's");
+        return SCROLL_ERR_CONFIG;
+    }
+    bool spliced = b->sp_n > 0;
+    for (const ScrollBatch::SpliceHost &sp : b->h_sp) spliced |= sp.w > 0;
+    if (spliced) {
+        set_err("scroll_batch_dyn_probe_hinted: a spliced slice carries MB types the probe does not follow: "
+                "clear the splices");
+        return SCROLL_ERR_CONFIG;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    int rc;
+    if (b->hd_dirty && (rc = hd_upload(b))) return rc;
+    if (b->hint_dirty && (rc = hint_upload(b))) return rc;
+    if ((rc = probe_alloc(b))) return rc;
+    ScrollBatch::Probe &p = b->pb;
+    if (!p.cls) {
+        hipError_t e = hipMalloc(&p.cls, (size_t)b->max_streams * (size_t)b->max_frames);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            set_err("scroll_batch_dyn_probe_hinted: %s", hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? SCROLL_ERR_OOM : SCROLL_ERR_HIP;
+        }
+    }
+    hipStream_t hs = hip_stream ? (hipStream_t)hip_stream : b->own;
+    const int S = b->nstreams, ld_fr = b->max_frames;
+    p.nframes = nframes;
+    p.nstreams = S;
+    p.nq = nq;
+    p.timed = 0;
+    p.hinted = 1;
+    if (S > 0 && nframes > 0) {
+        const bool timed = b->timing != 0;
+        if (timed && !p.ev[0]) {
+            HIPCHK(hipEventCreate(&p.ev[0]));
+            HIPCHK(hipEventCreate(&p.ev[1]));
+        }
+        if (timed) HIPCHK(hipEventRecord(p.ev[0], hs));
+        /* the compose's state pass: k_plan with PLAN_STATE reads the streams
+         * and commits nothing (no k_dyn_rows: the motion is the hints') */
+        DynGeom G = b->geo;
+        G.debug = b->debug;
+        const int plan = b->mode == SCROLL_MODE_EXPERIMENT ? SCROLL_PLAN_EXPERIMENT : SCROLL_PLAN_COMPOSER;
+        hipLaunchKernelGGL(k_plan, dim3(S), dim3(PLAN_THREADS), 0, hs, b->d_st, b->d_off, b->max_frames, p.nal,
+                           b->ld_nal, nframes, plan, b->debug | PLAN_STATE | PLAN_DYN, p.pend, p.dfr, ld_fr,
+                           nullptr, 0u, 0u, nullptr);
+        HIPCHK(hipGetLastError());
+        if (hprobe_launch(hs, nframes, S, b->d_st, p.nal, b->ld_nal, p.pend, p.dfr, ld_fr, b->d_hf, b->d_pool,
+                          b->d_spf, b->fallback, &G, b->d_src, b->d_refs, &Q, p.cls, p.res, p.done,
+                          timed ? p.ev[1] : nullptr)) {
+            set_err("k_hdyn_probe launch: %s", hipGetErrorString(hipGetLastError()));
+            return SCROLL_ERR_HIP;
+        }
+        p.timed = timed ? 1 : 0;
+    }
+    HIPCHK(hipEventRecord(p.fin, hs));
+    return SCROLL_OK;
+}
+
 int scroll_batch_dyn_probe_result(ScrollBatch *b, int s, int f, int k, ScrollDynProbe *out)
 {
     if (!b || !out) return SCROLL_ERR_ARG;
@@ -2633,6 +2730,16 @@ int scroll_batch_dyn_probe_result(ScrollBatch *b, int s, int f, int k, ScrollDyn
     DynFrame d;
     HIPCHK(hipMemcpy(&d, p.dfr + fi, sizeof(d), hipMemcpyDeviceToHost));
     if (d.nal < 0) return 1;
+    if (p.hinted) {
+        uint8_t c = 0;
+        HIPCHK(hipMemcpy(&c, p.cls + fi, 1, hipMemcpyDeviceToHost));
+        if (c == HPROBE_NONE) return 1;
+        if (c == HPROBE_FAIL) {
+            set_err("scroll_batch_dyn_probe_result: stream %d frame %d: a hint rect names a reference the frame "
+                    "lacks and the fallback is off (the compose would fail the stream)", s, f);
+            return SCROLL_ERR_CONFIG;
+        }
+    }
     uint32_t rows_in = 0;
     HIPCHK(hipMemcpy(&rows_in, p.done + fi, sizeof(rows_in), hipMemcpyDeviceToHost));
     if (rows_in != (uint32_t)b->geo.h) {

@@ -211,6 +211,8 @@ def _load():
                                                 P(ctypes.c_uint64)]),
         "scroll_batch_dyn_recon_ms": (ctypes.c_float, [ctypes.c_void_p]),
         "scroll_batch_dyn_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u8p, ctypes.c_int, ctypes.c_void_p]),
+        "scroll_batch_dyn_probe_hinted": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u8p, ctypes.c_int,
+                                                         ctypes.c_void_p]),
         "scroll_batch_dyn_probe_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                          P(ScrollDynProbe)]),
         "scroll_batch_dyn_probe_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t),
@@ -758,22 +760,29 @@ class Batch:
         return lib.scroll_batch_dyn_recon_ms(self.h)
 
     # ---- probing the rect at candidate QPs ----
-    def dyn_probe(self, nframes, qps, stream=None):
+    def dyn_probe(self, nframes, qps, stream=None, hinted=False):
         """what the next compose(nframes) of the plain dynamic rect would
         produce at each candidate QP, without committing anything
         (scroll_batch_dyn_probe): a numpy structured array [S][F][len(qps)]
         with fields sse (3 x u64: Y, Cb, Cr), bits, nonzero and valid (0: the
-        frame has no dynamic NAL, its other fields are 0)"""
+        frame has no dynamic NAL, its other fields are 0).  hinted: the rect
+        under UI hints instead (scroll_batch_dyn_probe_hinted); valid is 0
+        too for a frame without the rect, with a dormant fallback region, or
+        whose hints name a reference it lacks while the fallback is off"""
         import numpy as np
         q = bytes(int(v) if 0 <= int(v) <= 255 else 255 for v in qps)      # out of range: refused there
-        self._chk(lib.scroll_batch_dyn_probe(self.h, nframes, u8buf(q) if q else None, len(q), stream), "dyn_probe")
+        fn = lib.scroll_batch_dyn_probe_hinted if hinted else lib.scroll_batch_dyn_probe
+        self._chk(fn(self.h, nframes, u8buf(q) if q else None, len(q), stream),
+                  "dyn_probe_hinted" if hinted else "dyn_probe")
         out = np.zeros((self.num_streams, nframes, len(q)), dtype=_probe_dtype())
         r = ScrollDynProbe()
         for s in range(out.shape[0]):
             for f in range(nframes):
                 for k in range(len(q)):
-                    if self._chk(lib.scroll_batch_dyn_probe_result(self.h, s, f, k, ctypes.byref(r)),
-                                 "dyn_probe_result") == 1:
+                    rc = lib.scroll_batch_dyn_probe_result(self.h, s, f, k, ctypes.byref(r))
+                    if hinted and rc == SCROLL_ERR_CONFIG:     # that frame only: the compose would fail the stream
+                        break
+                    if self._chk(rc, "dyn_probe_result") == 1:
                         break
                     out[s, f, k] = ((r.sse[0], r.sse[1], r.sse[2]), r.bits, r.nonzero, 1)
         return out

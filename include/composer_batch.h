@@ -364,6 +364,46 @@ int scroll_batch_dyn_probe(ScrollBatch *b, int nframes, const uint8_t *qps, int 
 int scroll_batch_dyn_probe_result(ScrollBatch *b, int s, int f, int k, ScrollDynProbe *out);
 const ScrollDynProbe *scroll_batch_dyn_probe_device(ScrollBatch *b, size_t *stream_stride, size_t *frame_stride);
 float scroll_batch_dyn_probe_ms(ScrollBatch *b);   /* with enable_timing; -1 without */
+
+/* ---- the same probe for the rect under UI hints ----
+ * scroll_batch_dyn_probe_hinted(b, nframes, qps, nq, hip_stream) answers for
+ * the rect the next scroll_batch_compose(b, nframes) would code with UI hints
+ * set: the offsets, source, hint records, per-frame rect positions
+ * (scroll_batch_set_dyn_rect_at) and fallback setting as they stand; the
+ * frames' own QPs (scroll_batch_set_dyn_qp_at) are ignored.  Every rect MB
+ * takes the (ref, mv) of its topmost hint rect, else of its scroll row; a
+ * frame that falls back (scroll_batch_set_fallback) is probed as the whole
+ * picture without hint rects.  Arguments, candidate limit, argument errors
+ * and asynchrony are scroll_batch_dyn_probe's, results come through the
+ * accessors above, ScrollDynProbe means the same (sse: scroll_batch_dyn_sse
+ * after a hinted compose of that frame at q; an MB with
+ * coded_block_pattern 0 counts its one-bit code whether or not the composer
+ * then writes it as P_Skip), and nothing is committed: HintFrame flags,
+ * scroll_batch_fallback_frame and everything of the last compose stay.  It
+ * does the hint / position uploads the next compose would do anyway.
+ *
+ * From bits to a size: under hints slice_qp_delta is 0, the first rect MB
+ * with coded_block_pattern != 0 in raster order carries mb_qp_delta = q - 26
+ * and the others 0.  With
+ *     D(q) = len(se(q - 26)) - 1  if nonzero(q) > 0, else 0
+ * the scroll NAL's RBSP bits before the stop bit are
+ *     bits(q) + D(q) + C(frame)
+ * exactly in SCROLL_HINT_EXACT and SCROLL_HINT_SPEC; in SCROLL_HINT_PSKIP
+ * exactly while no rect MB is written as P_Skip and strictly more than the
+ * NAL otherwise (a skipped MB drops at least five header bits and lengthens
+ * a skip run by at most one): an upper bound that is safe for a budget.
+ * bits says nothing about an MB outgrowing its slot_bytes / (w h) region
+ * (SCROLL_ERR_OVERFLOW at the compose).
+ *
+ * SCROLL_ERR_CONFIG without a dynamic rect or references, without UI hints
+ * (that is scroll_batch_dyn_probe's case) and with any spliced slice in the
+ * batch.  scroll_batch_dyn_probe_result after it: 0; 1 (nothing written) for
+ * a frame without a dynamic NAL, without the rect (set_dyn_rect_at x0 = -1)
+ * or with a dormant fallback region that does not fall back;
+ * SCROLL_ERR_CONFIG for a frame -- that frame only -- whose hint rects name a
+ * reference it lacks while the fallback is off (the compose would fail the
+ * stream); SCROLL_ERR_DEVICE as above. */
+int scroll_batch_dyn_probe_hinted(ScrollBatch *b, int nframes, const uint8_t *qps, int nq, void *hip_stream);
 /* HIP-event ms of the timed composes since the last call: plan (both
  * passes), emit, dyn stage (= dyn code + dyn pack), dyn emit, dyn code
  * (k_dyn_rows + k_dyn_code), dyn pack (k_dyn_group + k_dyn_ep); accumulators reset
