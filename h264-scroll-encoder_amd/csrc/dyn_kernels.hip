@@ -3288,25 +3288,30 @@ __global__ __launch_bounds__(DT) void k_dyn_emit_gather(const DevStream *__restr
 }
 
 /* ---------------------------------------------------------------------- */
-/* k_dyn_gather: the dynamic rect's NALs -> arena, one chunk per thread on  */
-/* one straight path                                                        */
+/* k_dyn_gather: the dynamic rect's NALs -> arena, a run of GR chunks per    */
+/* thread                                                                   */
 /* ---------------------------------------------------------------------- */
-/* Round 4's replacement of k_dyn_emit_gather<., true> (≈440 VALU
- * instructions per 16-byte chunk there, in 64-bit index arithmetic, pick
- * trees and per-case branches).  Per 16-byte arena chunk inside the NAL:
+/* Round 4's replacement of k_dyn_emit_gather<., true>, since turned from one
+ * 16-byte chunk per thread to a run of GR consecutive chunks (neighbouring
+ * lanes take neighbouring runs): the searches are paid once per 16 GR bytes.
+ * Per run inside the NAL:
  *   K  = EP bytes before it (coarse index per 2^cs EBSP bytes + a short
  *        step over the sorted positions); its first RBSP byte i0 = u0 - K;
- *   R  = the 128 RBSP bits from byte i0: five row-stage words of the group
- *        holding them funnel-shifted by the bit phase, merged at a group
- *        seam with the next group's first four words (a 128-bit shift and
- *        mask, computed by every lane: no branch);
- *   each EP byte inside the chunk (sorted list, usually none): the tail
- *   shifts right one byte and 03 goes in;
- *   R byte-swapped -> one 16-byte store.
- * Chunks at the NAL's ends (start code, header, the last partial chunk) and
- * chunks meeting three groups (groups under 128 bits: tiny rects) take a
- * byte loop.  Grid (frames, streams, Z): workgroup z owns 1/Z of the NAL's
- * chunks. */
+ *   W  = GRW + 1 row-stage words of the group holding bit 8 i0.  Where the
+ *        group ends inside the run (a seam: one run in ~70 at config 3), the
+ *        next group's words are loaded so that they line up word for word
+ *        and are shifted into place -- only where a lane of the wave has a
+ *        seam;
+ *   O  = GRW funnel shifts of W by the bit phase;
+ *   each EP byte inside the run (sorted list): the tail shifts right one
+ *   byte and 03 goes in -- only where a lane has one;
+ *   O byte-swapped -> GR 16-byte stores.
+ * Runs at the NAL's ends (start code, header, the last partial run), runs cut
+ * by the workgroup's range and runs meeting three groups (a next group too
+ * short for the rest of the run: tiny rects, the static groups) go to a queue
+ * in LDS and are written by the whole workgroup, a byte per thread found by
+ * search (past SLOWQ runs: by the thread itself).  Grid (frames, streams, Z):
+ * workgroup z owns 1/Z of the NAL's chunks, in whole runs. */
 /* workgroups per NAL (grid z): one per ~640 rect MBs -- a config-3 NAL
  * (25 x 25 MBs, ~116 KB) keeps one (Z = 2 measured equal), the whole-picture
  * rects of the fallback (80 x 45: ~350 KB per NAL, 1,024 NALs = 4 workgroups
@@ -3326,31 +3331,15 @@ inline int gather_z(const DynGeom &g, int64_t nnal)
     if (nnal > 0 && z * nnal < GATHER_MIN_WG) z = (GATHER_MIN_WG + nnal - 1) / nnal;
     return (int)(z < 1 ? 1 : (z > 16 ? 16 : z));
 }
-/* Two chunk sets per thread in turn, the next chunk's loads in flight while
- * one is assembled (round 5: 0.142 against 0.146 ms per config-3 launch for
- * one chunk at a time, that form since removed).  Measured and not kept:
- * non-temporal arena stores (0.143), non-temporal row-stage loads (0.153) */
-
-/* 128-bit helpers on four words, word 0 most significant */
-struct W4 {
-    uint32_t w[4];
-};
-/* x >> s (logical), 0 <= s < 128 */
-__device__ inline W4 shr128(const W4 &x, uint32_t s)
-{
-    const uint32_t q = s >> 5, r = s & 31u;
-    uint32_t a[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        /* word k of the result: words k - q (hi part) and k - q - 1 */
-        const int i = k - (int)q;
-        const uint32_t hi = i >= 0 ? (i == 0 ? x.w[0] : (i == 1 ? x.w[1] : (i == 2 ? x.w[2] : x.w[3]))) : 0u;
-        const int j = i - 1;
-        const uint32_t lo = j >= 0 ? (j == 0 ? x.w[0] : (j == 1 ? x.w[1] : x.w[2])) : 0u;
-        a[k] = r ? __builtin_amdgcn_alignbit(lo, hi, r) : hi;
-    }
-    return W4{{a[0], a[1], a[2], a[3]}};
-}
+/* The next run's loads are in flight while this one's EP bytes go in and it
+ * is stored.  Runs of 2: 0.114 ms per config-3 launch against 0.149 for one
+ * chunk per thread; runs of 4 (lanes 64 bytes apart in every load and store,
+ * 11 registers spilled at 8 waves per SIMD) 0.155.  Measured and not kept
+ * with one chunk per thread: non-temporal arena stores (0.143 against 0.142
+ * ms), non-temporal row-stage loads (0.153) */
+constexpr int GR = 2;                    /* chunks per run (a power of two; 4 measured slower) */
+constexpr int GRW = 4 * GR;              /* RBSP words per run */
+constexpr int SLOWQ = 4;                 /* slow runs queued per workgroup and window (a NAL has ~3) */
 
 __global__ __launch_bounds__(DT) __attribute__((amdgpu_waves_per_eu(8))) void k_dyn_gather(const DevStream *__restrict__ st,
                                                   const NalDesc *__restrict__ nal, int ld_nal,
@@ -3393,13 +3382,17 @@ __global__ __launch_bounds__(DT) __attribute__((amdgpu_waves_per_eu(8))) void k_
     const uint32_t *fr = rowstage + nb * g.rs_frame_words;
     rs_table(gbits, nb, g, fr, goff, gb, gw, nullptr, t);
     const int ng = g.ngroups;
-    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(fr, 0xfffffffcu);   /* the frame's groups + spill slots */
+    /* the frame's groups + spill slots, bounded by the allocation: a run's
+     * loads reach up to GRW words past its group, and read 0 past the end */
+    const uint64_t rsb = 4u * (((uint64_t)g.rs_frames - nb) * g.rs_frame_words +
+                               (uint64_t)g.rs_spill_cap * g.rs_spill_words);
+    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(fr, (uint32_t)min(rsb, (uint64_t)0xfffffffcu));
     uint8_t *A = arena + (size_t)s * ld_arena;
     const uint64_t o0 = d.out_off, o1 = o0 + d.size;
     const uint8_t hdr[5] = {0, 0, 0, 1, nal_header_byte(0)};           /* nal.c:59-64 */
     const uint64_t cfirst = o0 >> 4;
     const uint32_t cnal = (uint32_t)(((o1 + 15) >> 4) - cfirst);
-    const uint32_t per = (cnal + gridDim.z - 1) / gridDim.z;
+    const uint32_t per = ((cnal + gridDim.z - 1) / gridDim.z + GR - 1) / GR * GR;   /* whole runs */
     const uint32_t cbeg = per * blockIdx.z, cend = min(cnal, cbeg + per);
     /* EBSP index of chunk c's byte 0: 16 c - d0 (d0 = o0 - 16 cfirst + 5) */
     const int32_t d0 = (int32_t)(o0 - (cfirst << 4)) + 5;
@@ -3414,125 +3407,146 @@ __global__ __launch_bounds__(DT) __attribute__((amdgpu_waves_per_eu(8))) void k_
      * (EP bytes before EBSP index ub + (b << cs)) */
     const bool whole = n <= wcap;
     __shared__ uint32_t win[3];                              /* kb, m, ce of the next window */
+    __shared__ uint32_t slowq[SLOWQ], nslow;                 /* the window's slow runs (first chunks) */
     uint32_t kb = 0, T = 0;
     int32_t ub = 0;
     int cs = 8, nblk = 1;
-    /* the NAL edges and three-group chunks: byte by byte */
-    auto slow_chunk = [&](uint32_t c, uint32_t K) {
-        uint8_t *q = A + ((cfirst + c) << 4);
-        for (int b = 0; b < 16; ++b) {
-            const uint64_t qa = ((cfirst + c) << 4) + (uint64_t)b;
-            if (qa < o0 || qa >= o1) continue;
-            const int32_t uu = (int32_t)(qa - o0) - 5;
-            uint8_t v;
-            if (uu < 0) {
-                v = hdr[qa - o0];
+    /* the NAL edges and runs meeting three groups: byte b of chunk c found
+     * by search (the coarse index, the positions, the group table) */
+    auto slow_byte = [&](uint32_t c, uint32_t b) {
+        const uint64_t qa = ((cfirst + c) << 4) + (uint64_t)b;
+        if (qa < o0 || qa >= o1) return;
+        const int32_t uu = (int32_t)(qa - o0) - 5;
+        uint8_t v;
+        if (uu < 0) {
+            v = hdr[qa - o0];
+        } else {
+            const int32_t du = uu - ub;
+            uint32_t K = raw[du > 0 ? min(du >> cs, nblk - 1) : 0];
+            while ((int32_t)(sp[K] + K) < uu) K++;
+            if ((int32_t)(sp[K] + K) == uu) {
+                v = 3;
             } else {
-                while ((int32_t)(sp[K] + K) < uu) K++;
-                if ((int32_t)(sp[K] + K) == uu) {
-                    v = 3;
-                } else {
-                    const uint32_t ri = (uint32_t)uu - K - kb;
-                    const uint32_t wd = rs_word(32u * (ri >> 2), ng, T, goff, gb, gw, fr);
-                    v = (uint8_t)(wd >> (8u * (3u - (ri & 3u))));
-                }
+                const uint32_t ri = (uint32_t)uu - K - kb;
+                const uint32_t wd = rs_word(32u * (ri >> 2), ng, T, goff, gb, gw, fr);
+                v = (uint8_t)(wd >> (8u * (3u - (ri & 3u))));
             }
-            q[b] = v;
         }
+        A[qa] = v;
     };
-    /* chunk c's 128 RBSP bits from its loads (x: 160 bits of the group from
-     * word lp >> 5, y: the next group's first 128 when the chunk runs past
-     * rem bits), the EP bytes inside it, stored */
-    auto fast_chunk = [&](uint32_t c, int32_t u0, uint32_t K, uint32_t lp, uint32_t rem, bool two, const uint32_t x[5],
-                          const uint32_t yb[4]) {
-        const uint32_t sh = lp & 31u;
-        W4 R;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) R.w[k] = sh ? __builtin_amdgcn_alignbit(x[k], x[k + 1], 32u - sh) : x[k];
-        if (two) {                                           /* rem bits of this group, then the next */
-            const W4 B = shr128(W4{{yb[0], yb[1], yb[2], yb[3]}}, rem);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t kb = 32u * (uint32_t)k;      /* bits of word k kept from this group */
-                const uint32_t keep = rem <= kb ? 0u : (rem >= kb + 32u ? 32u : rem - kb);
-                const uint32_t m = keep == 0u ? 0u : (keep == 32u ? 0xffffffffu : ~(0xffffffffu >> keep));
-                R.w[k] = (R.w[k] & m) | B.w[k];
-            }
-        }
-        /* the EP bytes inside the chunk: byte e becomes 03, the bytes from
-         * e on move one byte later */
-        for (uint32_t m = K;; ++m) {
-            const int32_t e = (int32_t)(sp[m] + m) - u0;
-            if (e >= 16) break;
-            const W4 S = shr128(R, 8u);
-            const uint32_t eb = 8u * (uint32_t)e;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t kb = 32u * (uint32_t)k;
-                const uint32_t keep = eb <= kb ? 0u : (eb >= kb + 32u ? 32u : eb - kb);
-                const uint32_t mk = keep == 0u ? 0u : (keep == 32u ? 0xffffffffu : ~(0xffffffffu >> keep));
-                /* the 03 byte: bits [eb, eb + 8) */
-                const uint32_t three = (eb >= kb && eb < kb + 32u) ? (3u << (24u - (eb - kb))) : 0u;
-                const uint32_t mk2 = (eb >= kb && eb < kb + 32u) ? (0xff000000u >> (eb - kb)) : 0u;
-                R.w[k] = (R.w[k] & mk) | (S.w[k] & ~mk & ~mk2) | three;
-            }
-        }
-        *reinterpret_cast<uint4 *>(A + ((cfirst + c) << 4)) =
-            make_uint4(__builtin_bswap32(R.w[0]), __builtin_bswap32(R.w[1]), __builtin_bswap32(R.w[2]),
-                       __builtin_bswap32(R.w[3]));
-    };
-    /* two chunk sets in turn (no register copies between them): chunk c +
-     * DT's search and loads go out before chunk c is assembled and stored.
-     * Every chunk loads (the edge / past-the-end ones at word 0, unused), so
+    /* A run (GR chunks from chunk c): the search and the run's GRW + 1
+     * row-stage words.  x starts one word early where the run starts on a
+     * word (s = 32), so one funnel shift by s = 1..32 serves every phase.
+     * Every run loads (the slow / past-the-end ones at word 0, unused), so
      * the number of loads in flight is fixed and the waits count them */
-    struct GSet {
-        uint32_t c, K, lp, rem;
+    struct GRun {
+        uint32_t c, K, s, rem, yo;                           /* yo: the next group's words, placed (two) */
         int32_t u0;
-        bool fast, two, yv;                                  /* yv: y holds the next group's words */
-        uint32_t x[5], y[4];
+        bool fast, two;                                      /* two: the run crosses into the next group */
+        uint32_t x[GRW + 1];
     };
     uint32_t wend = cend;                                    /* the window's chunk end */
-    auto prep = [&](uint32_t c, GSet &S) {
+    auto prep = [&](uint32_t c, GRun &S) {
         const int32_t u0 = 16 * (int32_t)c - d0, du = u0 - ub;
         uint32_t K = raw[du > 0 ? min(du >> cs, nblk - 1) : 0];
-        uint32_t wo = 0u, yo = 0u;
+        uint32_t wo = 0u;
         S.c = c;
         S.u0 = u0;
         S.fast = false;
         S.two = false;
-        S.yv = false;
-        S.lp = S.rem = 0u;
-        if (c < wend && u0 >= 0 && u0 + 16 <= nebsp) {
+        S.s = 32u;
+        S.rem = S.yo = 0u;
+        if (c + GR <= wend && u0 >= 0 && u0 + 16 * GR <= nebsp) {
             while ((int32_t)(sp[K] + K) < u0) K++;           /* sentinel stops it */
             const uint32_t i0 = (uint32_t)u0 - K - kb, P = 8u * i0;
             while (gg + 1 < ng && goff[gg + 1] <= P) ++gg;
             const uint32_t lp = P - goff[gg], rem = gb[gg] - lp;
-            const bool two = rem < 128u;
-            if (!two || gg + 1 >= ng || gb[gg + 1] >= 128u - rem) {
+            const uint32_t sh = lp & 31u, adj = sh ? 0u : 1u, wb = gw[gg] + (lp >> 5);
+            const uint32_t s = sh + 32u * adj, q = (s + rem) >> 5;
+            const bool two = rem < 128u * GR && gg + 1 < ng;
+            /* the next group holds the rest of the run (else three groups:
+             * slow), and no word before the frame's region is asked for */
+            if (wb >= adj && (!two || (gb[gg + 1] >= 128u * GR - rem && gw[gg + 1] >= q))) {
                 S.fast = true;
                 S.two = two;
-                S.lp = lp;
+                S.s = s;
                 S.rem = rem;
-                S.yv = two && gg + 1 < ng;
-                wo = 4u * (gw[gg] + (lp >> 5));
-                yo = S.yv ? 4u * gw[gg + 1] : wo;
+                wo = 4u * (wb - adj);
+                S.yo = two ? 4u * (gw[gg + 1] - q) : 0u;
             }
         }
         S.K = K;
-        const auto xa = __builtin_amdgcn_raw_buffer_load_b128(rr, wo, 0, 0);
-        const uint32_t x4 = __builtin_amdgcn_raw_buffer_load_b32(rr, wo + 16u, 0, 0);
-        const auto y = __builtin_amdgcn_raw_buffer_load_b128(rr, yo, 0, 0);
-        S.x[0] = (uint32_t)xa[0]; S.x[1] = (uint32_t)xa[1]; S.x[2] = (uint32_t)xa[2]; S.x[3] = (uint32_t)xa[3];
-        S.x[4] = x4;
-        S.y[0] = (uint32_t)y[0]; S.y[1] = (uint32_t)y[1]; S.y[2] = (uint32_t)y[2]; S.y[3] = (uint32_t)y[3];
-    };
-    auto finish = [&](GSet &S) {
-        if (S.fast) {
-            const uint32_t yb[4] = {S.yv ? S.y[0] : 0u, S.yv ? S.y[1] : 0u, S.yv ? S.y[2] : 0u, S.yv ? S.y[3] : 0u};
-            fast_chunk(S.c, S.u0, S.K, S.lp, S.rem, S.two, S.x, yb);
-        } else {
-            slow_chunk(S.c, S.K);
+#pragma unroll
+        for (int k = 0; k < GR; ++k) {
+            const auto xa = __builtin_amdgcn_raw_buffer_load_b128(rr, wo + 16u * (uint32_t)k, 0, 0);
+            S.x[4 * k] = (uint32_t)xa[0]; S.x[4 * k + 1] = (uint32_t)xa[1];
+            S.x[4 * k + 2] = (uint32_t)xa[2]; S.x[4 * k + 3] = (uint32_t)xa[3];
         }
+        S.x[GRW] = __builtin_amdgcn_raw_buffer_load_b32(rr, wo + 16u * GR, 0, 0);
+    };
+    /* the run's 128 GR RBSP bits from its words, the EP bytes inside it,
+     * stored.  Straight: GRW funnel shifts and byte swaps.  Across a seam
+     * (only where a lane of the wave has one): bit s + rem of x is the next
+     * group's bit 0, so its words are loaded q = (s + rem) / 32 words early
+     * and shifted right by the remaining r bits; word q is mixed */
+    auto assemble = [&](const GRun &S, uint32_t O[GRW]) {
+        uint32_t W[GRW + 1];
+#pragma unroll
+        for (int k = 0; k <= GRW; ++k) W[k] = S.x[k];
+        if (S.two) {
+            const uint32_t e = S.s + S.rem, q = e >> 5, r = e & 31u;
+            const uint32_t hm = ~(0xffffffffu >> r);         /* the r bits word q keeps */
+            uint32_t Y[GRW + 1];
+#pragma unroll
+            for (int k = 0; k < GR; ++k) {
+                const auto ya = __builtin_amdgcn_raw_buffer_load_b128(rr, S.yo + 16u * (uint32_t)k, 0, 0);
+                Y[4 * k] = (uint32_t)ya[0]; Y[4 * k + 1] = (uint32_t)ya[1];
+                Y[4 * k + 2] = (uint32_t)ya[2]; Y[4 * k + 3] = (uint32_t)ya[3];
+            }
+            Y[GRW] = __builtin_amdgcn_raw_buffer_load_b32(rr, S.yo + 16u * GR, 0, 0);
+#pragma unroll
+            for (int k = 0; k <= GRW; ++k) {
+                const uint32_t yp = k > 0 && (uint32_t)k > q ? Y[k > 0 ? k - 1 : 0] : 0u;
+                const uint32_t a = __builtin_amdgcn_alignbit(yp, Y[k], r);
+                const uint32_t keep = (uint32_t)k < q ? 0xffffffffu : ((uint32_t)k == q ? hm : 0u);
+                W[k] = (W[k] & keep) | ((uint32_t)k < q ? 0u : a);
+            }
+        }
+        const uint32_t fs = (32u - S.s) & 31u;
+#pragma unroll
+        for (int k = 0; k < GRW; ++k) O[k] = __builtin_amdgcn_alignbit(W[k], W[k + 1], fs);
+    };
+    auto emit = [&](uint32_t c, uint32_t K, int32_t u0, bool fast, uint32_t O[GRW]) {
+        if (!fast) {                                         /* queued for the whole workgroup, a byte per thread */
+            const uint32_t i = atomicAdd(&nslow, 1u);
+            if (i < (uint32_t)SLOWQ) {
+                slowq[i] = c;
+            } else {
+                for (uint32_t b = 0; b < 16u * GR; ++b)
+                    if (c + (b >> 4) < wend) slow_byte(c + (b >> 4), b & 15u);
+            }
+            return;
+        }
+        /* the EP bytes inside the run: byte e becomes 03, the bytes from e
+         * on move one byte later (the run's last byte drops out) */
+        for (uint32_t m = K;; ++m) {
+            const int32_t e = (int32_t)(sp[m] + m) - u0;
+            if (e >= 16 * GR) break;
+#pragma unroll
+            for (int k = GRW - 1; k >= 0; --k) {
+                const int32_t d = 8 * e - 32 * k;            /* the 03 byte's bit in word k */
+                const uint32_t sk = __builtin_amdgcn_alignbit(k ? O[k > 0 ? k - 1 : 0] : 0u, O[k], 8u);
+                const uint32_t dd = (uint32_t)d & 31u;
+                const uint32_t km = ~(0xffffffffu >> dd);    /* the bits before it */
+                const uint32_t mix = (O[k] & km) | (sk & ~km & ~(0xff000000u >> dd)) | (3u << (24u - dd));
+                O[k] = d >= 32 ? O[k] : (d < 0 ? sk : mix);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < GR; ++k)
+            *reinterpret_cast<uint4 *>(A + ((cfirst + c + (uint32_t)k) << 4)) =
+                make_uint4(__builtin_bswap32(O[4 * k]), __builtin_bswap32(O[4 * k + 1]),
+                           __builtin_bswap32(O[4 * k + 2]), __builtin_bswap32(O[4 * k + 3]));
     };
     for (uint32_t cb = cbeg; cb < cend; cb = wend) {
         uint32_t m = n;
@@ -3566,7 +3580,10 @@ __global__ __launch_bounds__(DT) __attribute__((amdgpu_waves_per_eu(8))) void k_
             wend = win[2];
         }
         for (uint32_t i = t; i < m; i += DT) (sorted ? sp : raw)[i] = el[kb + i] + kb;
-        if (t == 0) sp[m] = 0x3fffffffu;                     /* sentinel: sp[m] + m never before a chunk */
+        if (t == 0) {
+            sp[m] = 0x3fffffffu;                             /* sentinel: sp[m] + m never before a chunk */
+            nslow = 0u;
+        }
         __syncthreads();
         for (uint32_t i = t; i < (sorted ? 0u : m); i += DT) {   /* ep_scan's lists (whole only): by rank */
             const uint32_t v = raw[i];
@@ -3595,17 +3612,28 @@ __global__ __launch_bounds__(DT) __attribute__((amdgpu_waves_per_eu(8))) void k_
         }
         __syncthreads();
         if (stp && cb == cbeg) stp[1] = __builtin_amdgcn_s_memrealtime();
-        GSet sa, sb;
-        uint32_t c = cb + (uint32_t)t;
-        if (c < wend) prep(c, sa);
+        /* one register set: a run's words are dead once shifted into O, so
+         * the next run's search and loads go out before the EP bytes and the
+         * stores of this one */
+        GRun S;
+        uint32_t c = cb + (uint32_t)(GR * t);
+        if (c < wend) prep(c, S);
         while (c < wend) {
-            prep(c + DT, sb);
-            finish(sa);
-            c += DT;
-            if (c >= wend) break;
-            prep(c + DT, sa);
-            finish(sb);
-            c += DT;
+            uint32_t O[GRW];
+            const uint32_t K = S.K;
+            const int32_t u0 = S.u0;
+            const bool fast = S.fast;
+            assemble(S, O);
+            prep(c + GR * DT, S);
+            emit(c, K, u0, fast, O);
+            c += GR * DT;
+        }
+        /* the queued slow runs, a byte per thread */
+        __syncthreads();
+        const uint32_t nq = min(nslow, (uint32_t)SLOWQ);
+        for (uint32_t i = (uint32_t)t; i < nq * 16u * GR; i += DT) {
+            const uint32_t cq = slowq[i / (16u * GR)] + ((i / 16u) & (uint32_t)(GR - 1));
+            if (cq < wend) slow_byte(cq, i & 15u);
         }
     }
     if (stamps) {                                            /* uniform */
