@@ -1,0 +1,233 @@
+/*
+ * batch.h -- internal to the host-side batch engine behind
+ * include/composer_batch.h: the batch's state and what its files share.
+ *   batch_core.hip    create / destroy, streams, compose, sync, output, timing
+ *   batch_dyn.hip     the dynamic rect, its reconstruction and its QP probe
+ *   batch_hint.hip    UI hints, the rect under hints, the splice
+ *   batch_ingest.hip  ingest, I_PCM files, reference updates
+ *   batch_dropin.hip  the synchronous drop-in helpers of engine.h
+ * Nothing here enters the library's dynamic symbol table.
+ */
+#ifndef SCROLL_BATCH_H
+#define SCROLL_BATCH_H
+
+#include <hip/hip_runtime.h>
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "engine.h"
+#include "dyn_engine.h"         /* DynScratch, DynFork */
+#include "splice_engine.h"      /* SpliceFrame, SpliceMbRec, SpliceUnit */
+#include "ingest_engine.h"      /* IngestFile, IngestScan, IngestOut */
+
+/* (set_err: scroll::batch's, below) */
+#define HIPCHK(x)                                                                  \
+    do {                                                                           \
+        hipError_t e_ = (x);                                                       \
+        if (e_ != hipSuccess) {                                                    \
+            set_err("%s failed: %s", #x, hipGetErrorString(e_));                   \
+            return SCROLL_ERR_HIP;                                                 \
+        }                                                                          \
+    } while (0)
+
+/* ======================================================================== */
+/* ScrollBatch                                                              */
+/* ======================================================================== */
+/* (the public headers' opaque type: global, and outside the hidden region
+ * below, which would take its implicit members' symbols out of the library) */
+constexpr int NEV = 7;
+struct ScrollBatch {
+    int device = 0;
+    int mode = SCROLL_MODE_COMPOSER;
+    int max_streams = 0, max_frames = 0, nstreams = 0;
+    int debug = 0;
+    size_t arena_bytes = 0, ld_arena = 0;
+    int ld_nal = 0;
+    DevStream *d_st = nullptr;
+    DevStream *h_st = nullptr;
+    int32_t *d_off = nullptr;
+    NalDesc *d_nal = nullptr;
+    uint8_t *d_arena = nullptr;
+    hipStream_t own = nullptr;
+    hipStream_t last = nullptr;
+    hipEvent_t ev[NEV] = {};
+    int timing = 0;
+    int timed_pending = 0;
+    float ms[6] = {0, 0, 0, 0, 0, 0};  /* plan, emit, dyn stage, dyn emit, dyn code, dyn pack */
+    std::vector<hipEvent_t> ring;      /* NEV events per timed compose, pending */
+    std::vector<uint8_t> ring_dyn;     /* per pending compose: 1 the dynamic-rect pipeline ran, 2 lite timing */
+    int ev_dyn = 0;                    /* the same for b->ev */
+    int ring_used = 0;
+    double acc_ms[6] = {0, 0, 0, 0, 0, 0};
+    int acc_n = 0;
+    int host_valid = 1;
+    int last_plan_mode = SCROLL_PLAN_COMPOSER;
+    int last_nframes = 0;
+    std::vector<NalDesc> nal_cache;
+    int nal_cache_valid = 0;
+    uint64_t *d_dbg = nullptr;
+    size_t dbg_slots = 0;
+    /* dynamic rect (configs 3-5) */
+    PlanPending *d_pend = nullptr;
+    int dyn_on = 0;
+    int dyn_pw = 0, dyn_ph = 0;        /* picture size every stream must have      */
+    int dyn_refs = 0;                  /* 0 unset, 1 shared pair, 2 per stream     */
+    DynGeom geo{};
+    DynFrame *d_dfr = nullptr;
+    uint8_t *d_src = nullptr, *d_refs = nullptr, *d_stage = nullptr;
+    DynScratch dx{};                   /* rows, block records, look-back words of the dynamic coder */
+    /* the rect's reconstruction (scroll_batch_set_dyn_recon, recon_kernels.hip) */
+    int recon_on = 0;
+    uint8_t *d_rec = nullptr;          /* decoded rects, d_src's layout and strides          */
+    unsigned long long *d_sse = nullptr;   /* [max_streams * max_frames][3]: Y, Cb, Cr       */
+    hipEvent_t rc_ev[2] = {};          /* timing: around k_dyn_recon (created on first use)  */
+    int rc_timed = 0;                  /* the last compose recorded them                     */
+    /* ... under UI hints (scroll_batch_set_dyn_recon_hinted, hrecon_kernels.hip) */
+    int recon_hinted = 0;
+    int rc_last_hint = 0;              /* the last compose ran k_hdyn_recon                  */
+    std::vector<int> rc_fail;          /* [stream]: the status scroll_batch_sync reported for that compose */
+    /* the QP probe (scroll_batch_dyn_probe, probe_kernels.hip): a trial plan
+     * and its prediction rows in buffers of its own, so that nothing of the
+     * batch's state is touched; allocated by the first probe */
+    struct Probe {
+        NalDesc *nal = nullptr;
+        DynFrame *dfr = nullptr;
+        PlanPending *pend = nullptr;
+        uint32_t *rows = nullptr, *ctr = nullptr, *done = nullptr;
+        uint4 *heads = nullptr;
+        ScrollDynProbe *res = nullptr;  /* [max_streams * max_frames][SCROLL_DYN_PROBE_MAX_QPS] */
+        uint8_t *cls = nullptr;         /* [max_streams * max_frames]: k_hprobe_class (scroll_batch_dyn_probe_hinted) */
+        int hinted = 0;                 /* the last probe was the hinted one */
+        int nframes = -1, nstreams = 0, nq = 0;   /* the last probe; nframes -1: none */
+        hipEvent_t fin = nullptr;       /* recorded after the last probe's launches */
+        hipEvent_t ev[2] = {};          /* timing: around them (created on first use) */
+        int timed = 0;
+    } pb;
+    /* UI hints: staged like the dynamic rect (shares
+     * d_dfr, d_stage and geo.slot_bytes; the two are exclusive) */
+    int hint_on = 0;
+    int hint_dirty = 0;
+    int hint_max_mb = 0;               /* MBs per picture the slots are sized for */
+    std::vector<std::vector<ScrollHintRect>> h_hint;   /* [s * max_frames + f] */
+    std::vector<int16_t> h_hint_mode;
+    HintFrame *d_hf = nullptr;
+    ScrollHintRect *d_pool = nullptr;
+    size_t pool_cap = 0;
+    /* pre-encoded MB splice: frames of the hint path
+     * whose rect comes from an external slice */
+    struct SpliceHost {
+        int x0 = 0, y0 = 0, w = 0, h = 0;
+        std::vector<uint8_t> nal;      /* host bytes (scroll_batch_set_splice)          */
+        const uint8_t *dnal = nullptr; /* or device bytes (scroll_batch_set_splices_device) */
+        size_t n = 0;
+    };
+    std::vector<SpliceHost> h_sp;      /* [s * max_frames + f]; w = 0: none */
+    /* the dynamic rect under UI hints (hdyn_kernels.hip): with both on,
+     * every frame's rect MBs are coded by k_hdyn_code into splice records
+     * (d_sp_rec, word pool d_sp_rbsp) and composed by k_splice_stage */
+    std::vector<int32_t> h_dyn_pos;    /* [2 (s * max_frames + f)]: rect origin, x0 < 0: none */
+    int fallback = 0;                  /* scroll_batch_set_fallback: k_hint_fb before the stage kernels */
+    DynFork fork{};                    /* SCROLL_DYN_FORK=1: the general path + static groups beside k_dyn_row */
+    std::vector<int32_t> h_dyn_qp;     /* [s * max_frames + f]: the frame's rect QP under hints, -1: the stream's */
+    int dyn_pos_custom = 0;            /* some frame's origin differs from the batch rect */
+    int dyn_qp = 26;                   /* the rect's QP (scroll_batch_set_dyn_qp)          */
+    int hd_dirty = 0;                  /* d_spf / HintFrame of the combined frames out of date */
+    uint32_t hd_mb_words = 0;          /* pool words per rect MB */
+    size_t dyn_cap = 0;                /* the dynamic rect's own staging cap (geo.slot_bytes without hints) */
+    int sp_n = 0;                      /* spliced frames                           */
+    int sp_dirty = 0;                  /* upload + parse before the next compose   */
+    int sp_parse = 0;                  /* k_splice_parse pending                   */
+    SpliceFrame *d_spf = nullptr;      /* [max_streams * max_frames]               */
+    uint8_t *d_sp_nal = nullptr;
+    uint32_t *d_sp_rbsp = nullptr;
+    SpliceMbRec *d_sp_rec = nullptr;
+    int32_t *d_sp_list = nullptr;
+    SpliceUnit *d_sp_units = nullptr;  /* NAL unit slots (splice_unit_cap per frame) */
+    int32_t *d_sp_lanes = nullptr;     /* lane list: count (zero between parses), (list index, unit) pairs */
+    size_t sp_lanes_cap = 0, sp_nslots = 0;
+    int sp_ymax = 1;                   /* most unit slots of a frame (parse grid y)  */
+    size_t sp_nal_cap = 0, sp_rbsp_cap = 0, sp_rec_cap = 0, sp_list_cap = 0, sp_units_cap = 0;
+    /* stream ingest: scratch, grown on demand */
+    uint8_t *d_ing_in = nullptr;
+    size_t ing_in_cap = 0;
+    IngestFile *d_ing_files = nullptr;
+    IngestScan *d_ing_scan = nullptr;
+    IngestOut *d_ing_out = nullptr;
+    int ing_cap = 0;
+    void *d_ing_work = nullptr;                 /* segmented ingest scratch */
+    size_t ing_work_bytes = 0;
+    hipEvent_t ing_ev[2] = {};         /* timing: around the ingest kernels */
+    /* reference files from pictures: EP count per chunk */
+    uint32_t *d_ipcm_cnt = nullptr;
+    size_t ipcm_cap = 0;
+    uint8_t *d_ipcm_stg = nullptr;              /* count pass RBSP for the write pass */
+    size_t ipcm_stg_cap = 0;
+    /* the one pass: the chunks' hand-off words */
+    unsigned long long *d_ipcm_hw = nullptr;
+    size_t ipcm_hw_cap = 0;
+    uint32_t ipcm_epoch = 0;
+    double ipcm_ms = 0.0;
+    int ipcm_n = 0;
+    /* the asynchronous I_PCM calls since the last sync: their overflow flag
+     * (checked at the sync) and, with timing, their event pairs */
+    uint32_t *ipcm_over = nullptr;      /* = d_ipcm_sticky while calls are pending */
+    uint32_t *d_ipcm_sticky = nullptr;
+    size_t ipcm_over_stride = 0;
+    std::vector<hipEvent_t> ipcm_ev;    /* pairs, reused */
+    size_t ipcm_ev_used = 0;
+    double ing_ms = 0.0;
+    int ing_n = 0;
+    /* host delivery: per-stream (offset, bytes) table of the last packing */
+    int dyn_grow = 0;                  /* the dynamic rect's pools at their bounds (after running out) */
+    int32_t *d_upd = nullptr;          /* reference updates: (stream, which) per entry */
+    size_t upd_cap = 0;
+    uint64_t *d_out_tab = nullptr;
+    size_t out_tab_cap = 0;
+    hipEvent_t out_ev = nullptr;
+};
+
+#pragma GCC visibility push(hidden)
+namespace scroll {
+namespace batch {
+
+/* ---- batch_core.hip ---- */
+void set_err(const char *fmt, ...);
+int usable_devices(std::vector<int> *ids);
+int check_cfg(const ComposerConfig *c);
+void cfg_to_dev(const ComposerConfig *c, DevStream *d);
+void dev_to_cfg(const DevStream *d, ComposerConfig *c);
+hipError_t timing_event(hipEvent_t *e);
+/* `who` could not allocate (or otherwise failed with e): the message
+ * "who: error", the sticky error cleared on request, SCROLL_ERR_OOM or
+ * SCROLL_ERR_HIP */
+int hip_fail(const char *who, hipError_t e, bool clear = false);
+int dev_grow(void **p, size_t *cap, size_t n, size_t size, const char *who);
+int batch_host_sync(ScrollBatch *b);
+int launch(ScrollBatch *b, int nframes, int plan_mode, int nal_max, hipStream_t hs, int plan_flags = 0);
+int stream_fail_code(ScrollBatch *b, int s);
+int load_nals(ScrollBatch *b);
+
+/* ---- batch_dyn.hip ---- */
+void probe_release(ScrollBatch *b);
+void dyn_release(ScrollBatch *b);
+int dyn_grow_pools(ScrollBatch *b);
+
+/* ---- batch_hint.hip ---- */
+int hint_upload(ScrollBatch *b);
+int hd_setup(ScrollBatch *b);
+int hd_upload(ScrollBatch *b);
+int splice_upload(ScrollBatch *b);
+int splice_frame_status(ScrollBatch *b, size_t i, int *status);
+const char *splice_msg(int e);
+
+/* ---- batch_ingest.hip ---- */
+int ipcm_async_check(ScrollBatch *b);
+
+}  // namespace batch
+}  // namespace scroll
+#pragma GCC visibility pop
+
+#endif

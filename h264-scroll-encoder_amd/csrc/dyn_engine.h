@@ -1,6 +1,7 @@
 /*
  * dyn_engine.h -- engine-internal launchers of the dynamic-rect kernels
- * (dyn_kernels.hip), used by the batch engine (scroll_kernels.hip).
+ * (dyn_kernels.hip), used by the batch engine (batch_core.hip,
+ * batch_dyn.hip).
  */
 #ifndef SCROLL_DYN_ENGINE_H
 #define SCROLL_DYN_ENGINE_H

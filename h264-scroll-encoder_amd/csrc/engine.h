@@ -1,6 +1,7 @@
 /*
  * engine.h -- internal interface between the host C drop-in layer
- * (composer.c, h264_writer.c) and the HIP engine (scroll_kernels.hip).
+ * (composer.c, h264_writer.c) and the HIP engine (batch_dropin.hip; the
+ * device structs: every kernel file).
  * Not installed; the public ABI is the headers in include/.
  */
 #ifndef SCROLL_ENGINE_H

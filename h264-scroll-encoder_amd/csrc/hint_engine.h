@@ -1,6 +1,6 @@
 /*
  * hint_engine.h -- host-side launcher of the UI-hint stage kernel
- * (hint_kernels.hip); the batch (scroll_kernels.hip) drives it between the
+ * (hint_kernels.hip); the batch (batch_core.hip) drives it between the
  * plan's state and size passes, like the dynamic-rect coder.
  */
 #pragma once

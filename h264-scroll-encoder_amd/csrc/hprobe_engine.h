@@ -1,7 +1,7 @@
 /*
  * hprobe_engine.h -- engine-internal launcher of the QP probe of the dynamic
  * rect under UI hints (hprobe_kernels.hip), used by the batch engine
- * (scroll_kernels.hip) for scroll_batch_dyn_probe_hinted.
+ * (batch_dyn.hip) for scroll_batch_dyn_probe_hinted.
  */
 #ifndef SCROLL_HPROBE_ENGINE_H
 #define SCROLL_HPROBE_ENGINE_H

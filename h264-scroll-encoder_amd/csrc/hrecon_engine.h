@@ -1,7 +1,7 @@
 /*
  * hrecon_engine.h -- engine-internal launcher of the dynamic rect's
  * reconstruction under UI hints (hrecon_kernels.hip), used by the batch
- * engine (scroll_kernels.hip) when scroll_batch_set_dyn_recon_hinted is on.
+ * engine (batch_core.hip) when scroll_batch_set_dyn_recon_hinted is on.
  */
 #ifndef SCROLL_HRECON_ENGINE_H
 #define SCROLL_HRECON_ENGINE_H

@@ -15,7 +15,7 @@
  *           whole 16-byte lines stored aligned, edge lines byte by byte
  *   one pass (round 6, IP_ONEPASS, opt-in: SCROLL_IPCM_ONEPASS=1, when
  *           out_stride holds the worst case so no file can overflow; less
- *           traffic, more time -- scroll_kernels.hip): both in one workgroup -- the chunk's EP
+ *           traffic, more time -- batch_ingest.hip): both in one workgroup -- the chunk's EP
  *           count published, the counts of the earlier chunks of its file
  *           found by a decoupled look-back (workgroups start in grid order,
  *           so every earlier chunk has started or will), the bytes written

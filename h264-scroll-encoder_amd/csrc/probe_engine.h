@@ -1,6 +1,6 @@
 /*
  * probe_engine.h -- engine-internal launcher of the dynamic rect's QP probe
- * (probe_kernels.hip), used by the batch engine (scroll_kernels.hip) for
+ * (probe_kernels.hip), used by the batch engine (batch_dyn.hip) for
  * scroll_batch_dyn_probe.
  */
 #ifndef SCROLL_PROBE_ENGINE_H

@@ -1,7 +1,7 @@
 /*
  * recon_engine.h -- engine-internal launcher of the dynamic rect's
  * reconstruction kernel (recon_kernels.hip), used by the batch engine
- * (scroll_kernels.hip) when scroll_batch_set_dyn_recon is on.
+ * (batch_core.hip) when scroll_batch_set_dyn_recon is on.
  */
 #ifndef SCROLL_RECON_ENGINE_H
 #define SCROLL_RECON_ENGINE_H

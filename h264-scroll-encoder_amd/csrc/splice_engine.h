@@ -1,6 +1,6 @@
 /*
  * splice_engine.h -- host-side launchers of the pre-encoded MB splice
- * (splice_kernels.hip).  The batch (scroll_kernels.hip)
+ * (splice_kernels.hip).  The batch (batch_core.hip)
  * runs k_splice_parse when the spliced slices change and k_splice_stage
  * beside k_hint_stage between the plan's state and size passes.
  */
