@@ -254,17 +254,20 @@ int launch(ScrollBatch *b, int nframes, int plan_mode, int nal_max, hipStream_t 
         if (!lite) b->ev_dyn = dyn ? 1 : 0;
     }
     const int ld_fr = b->max_frames;
+    /* k_plan's own flags start at PLAN_REWIND: the debug bits from there up
+     * (SCROLL_DEBUG_DYN_STAMPS is the same bit) are not for it */
+    const int plan_debug = b->debug & (PLAN_REWIND - 1);
     int rc = mark(0);
     if (rc) return rc;
     if (!dyn) {
         scroll_launch_plan(hs, S, b->d_st, b->d_off, b->max_frames, b->d_nal, b->ld_nal, nframes, plan_mode,
-                           b->debug | plan_flags, b->d_pend, b->d_dfr, ld_fr);
+                           plan_debug | plan_flags, b->d_pend, b->d_dfr, ld_fr);
         HIPCHK(hipGetLastError());
         if ((rc = mark(1)) || (rc = mark(2)) || (rc = mark(3))) return rc;
     } else {
         const bool dyn_rect = b->dyn_on && !hint;
         scroll_launch_plan(hs, S, b->d_st, b->d_off, b->max_frames, b->d_nal, b->ld_nal, nframes, plan_mode,
-                           b->debug | plan_flags | PLAN_STATE | PLAN_DYN, b->d_pend, b->d_dfr,
+                           plan_debug | plan_flags | PLAN_STATE | PLAN_DYN, b->d_pend, b->d_dfr,
                            ld_fr, nullptr, 0u, 0u, dyn_rect ? b->dx.ctr : nullptr);
         HIPCHK(hipGetLastError());
         if ((rc = mark(1))) return rc;
@@ -379,7 +382,7 @@ int launch(ScrollBatch *b, int nframes, int plan_mode, int nal_max, hipStream_t 
         }
         if ((rc = mark(2))) return rc;
         scroll_launch_plan(hs, S, b->d_st, b->d_off, b->max_frames, b->d_nal, b->ld_nal, nframes, plan_mode,
-                           b->debug | plan_flags | PLAN_SIZE | PLAN_DYN, b->d_pend, b->d_dfr,
+                           plan_debug | plan_flags | PLAN_SIZE | PLAN_DYN, b->d_pend, b->d_dfr,
                            ld_fr, (b->dyn_on && !b->hint_on) ? (const uint32_t *)b->dx.ctr : nullptr,
                            b->geo.rs_spill_cap, b->geo.gen_cap);
         HIPCHK(hipGetLastError());

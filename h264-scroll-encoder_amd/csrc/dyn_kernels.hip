@@ -585,14 +585,18 @@ typedef OrSink<LdsOrWin> WSink;
 __device__ inline int tc_of(uint32_t m) { return (int)((m >> 8) & 31u); }
 
 /* the head codeword classes of a NAL (3 row types x first / middle / last) */
-struct HeadCtx {
-    Regions rg;
-    int a_end, mbw, nrefs;
+/* which class an MB takes: all that k_dyn_row keeps of a NAL's HeadCtx */
+struct HeadSel {
+    int a_end, mbw;
     __device__ inline int sel(int row, int col) const
     {
         const bool curA = row < a_end, abvA = (row - 1) < a_end;
         return 3 * (row == 0 ? 0 : (curA ? 1 : (abvA ? 2 : 3))) + (col == 0 ? 0 : (col == mbw - 1 ? 2 : 1));
     }
+};
+struct HeadCtx : HeadSel {
+    Regions rg;
+    int nrefs;
     /* head of class cls (h264_writer.c:434-453 after the row-uniform predictor) */
     template <class S>
     __device__ inline void put_class(S &sk, int cls) const
@@ -627,6 +631,15 @@ __device__ inline HeadCtx head_ctx(const NalCtx &c)
     H.a_end = (c.h - c.off) / 16;
     H.mbw = c.w / 16;
     H.nrefs = 2 + c.nwp;
+    return H;
+}
+
+/* head_ctx(nal_ctx(S, d, ...))'s HeadSel alone */
+__device__ inline HeadSel head_sel(const DevStream *S, const NalDesc &d)
+{
+    HeadSel H;
+    H.a_end = (S->h - d.off) / 16;
+    H.mbw = S->w / 16;
     return H;
 }
 
@@ -764,11 +777,15 @@ __device__ __attribute__((noinline)) uint32_t ovf_bits(const PTabs &PT, const Ta
 }
 
 /* the sink lives in the callee: a sink passed by reference would be kept in
- * scratch memory by the caller on its every put */
-__device__ __attribute__((noinline)) void ovf_put(uint32_t *buf, uint32_t lo, uint32_t n, uint32_t pos,
+ * scratch memory by the caller on its every put.  The window comes as an LDS
+ * pointer: for a generic one the caller kept the LDS aperture's high word
+ * through the piece loop (a spilled SGPR, reloaded at the call) */
+typedef __attribute__((address_space(3))) uint32_t *LdsWords;
+__device__ __attribute__((noinline)) void ovf_put(LdsWords win, uint32_t lo, uint32_t n, uint32_t pos,
                                                   const PTabs &PT, const Tabs &TB, uint4 bd, const uint4 *bw, int pc,
                                                   int nC)
 {
+    uint32_t *buf = (uint32_t *)win;
     WSink sk{LdsOrWin{buf, lo, n}, 0, 0, 0};
     sk.start(pos);
     ovf_code(sk, PT, TB, bd, bw, pc, nC);
@@ -1220,7 +1237,9 @@ __device__ inline void put_piece1(uint32_t *buf, uint32_t pos, uint32_t tv, uint
  * in global memory instead of steps 1-2. */
 constexpr int ROW_MAXT = 1024;
 /* waves per SIMD the register allocation targets: 8 (eight row workgroups
- * per CU; the SGPR budget then spills some uniform values to VGPR lanes).
+ * per CU; the SGPR budget then parks some uniform values in VGPR lanes
+ * across the levels phase -- none is written or read inside a hot loop,
+ * tools/row_regs.py lists them per phase and loop).
  * With the general path in its own instantiation the normal one needs 53
  * VGPRs and 8 beat 7 (1.43 against 1.50 ms); with both paths in one kernel
  * (63 VGPRs) the spills ate the gain */
@@ -1452,36 +1471,90 @@ __device__ inline int row_slot(int task, int w)
     return (int)__umul24((uint32_t)k, (uint32_t)NPC) + pc;   /* no quarter-rate multiply */
 }
 
+/* k_dyn_row's arguments as ONE trivially-copyable struct: the kernel's only
+ * parameter, so a field's offsetof is its offset in the kernel-argument
+ * segment.  A uniform value named as a parameter is loaded in the entry
+ * block and kept (or spilled to a VGPR lane and reloaded) to the kernel's
+ * end; most of these are used in one phase only.  The kernel therefore
+ * names only the fields its prologue and pixel loop use (the first group)
+ * and reads the others from the argument segment where they are used
+ * (row_arg below): scalar loads at the head of a phase instead of registers
+ * held, or lane traffic, all kernel long. */
+struct RowArgs {
+    /* entry block: the prologue and the levels loop */
+    DevStream *st;
+    const NalDesc *nal;
+    const PlanPending *pend;
+    DynFrame *dfr;
+    const uint32_t *rows;
+    const uint8_t *src, *refs;
+    const uint4 *heads;
+    int32_t ld_nal, ld_fr;
+    DynGeom g;                  /* named: the rect, pw / ph, the source / reference strides */
+    /* the hand-off: the publish after the levels, the poll before phase 3 */
+    unsigned long long *tcx;
+    uint32_t epoch, pad0;
+    /* phase 5 (g's ngroups and rs_* fields with them) */
+    uint32_t *rowstage, *gbits, *spill, *ctr;
+    /* the general path's records (GEN) */
+    const uint16_t *meta;
+    const uint2 *blo, *bhi;
+    const uint4 *bwd;
+    /* the debug instantiations (DBG) */
+    uint64_t *stamps;
+};
+static_assert(std::is_trivially_copyable<RowArgs>::value && std::is_standard_layout<RowArgs>::value,
+              "RowArgs is copied into the kernel-argument segment as it is: offsetof = kernarg offset");
+static_assert(offsetof(RowArgs, st) == 0 && alignof(RowArgs) == 8 && sizeof(RowArgs) % 8 == 0,
+              "the only kernel parameter starts the kernel-argument segment");
+static_assert(offsetof(RowArgs, tcx) % 16 == 0 && offsetof(RowArgs, epoch) == offsetof(RowArgs, tcx) + 8,
+              "tcx and epoch: one 16-byte scalar load");
+static_assert(offsetof(RowArgs, gbits) == offsetof(RowArgs, rowstage) + 8 &&
+                  offsetof(RowArgs, ctr) == offsetof(RowArgs, rowstage) + 24,
+              "phase 5's four pointers are adjacent");
+
+/* the kernel-argument segment at this point of the program: the pointer
+ * goes through an empty asm, so loads through it are issued here, not
+ * hoisted to the entry block, and in the constant address space, so they
+ * are scalar loads (without it: flat loads into VGPRs) */
+typedef const char __attribute__((address_space(4))) *KargPtr;
+__device__ inline KargPtr kargs_here()
+{
+    KargPtr p = (KargPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+template <class T>
+__device__ inline T karg_at(KargPtr p, size_t off)
+{
+    return *reinterpret_cast<const T __attribute__((address_space(4))) *>(p + off);
+}
+/* field F of the kernel's RowArgs through K = kargs_here() */
+#define row_arg(K, F) karg_at<decltype(RowArgs::F)>(K, offsetof(RowArgs, F))
+
 /* grid (h, frames, streams), row_threads(w) threads, row_lds_bytes dynamic LDS.
  * GEN: the instantiation for the NALs k_dyn_rows flagged for the general
  * path (records from k_dyn_code_general); the other one codes the rest --
  * each returns at once for the other's NALs, and neither carries the
- * other's code (registers) */
-template <bool GEN>
-__global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL_ROW_WAVES))) void k_dyn_row(DevStream *__restrict__ st,
-                                                     const NalDesc *__restrict__ nal, int ld_nal,
-                                                     const PlanPending *__restrict__ pend,
-                                                     DynFrame *__restrict__ dfr, int ld_fr, DynGeom g,
-                                                     const uint32_t *__restrict__ rows,
-                                                     const uint8_t *__restrict__ src,
-                                                     const uint8_t *__restrict__ refs,
-                                                     const uint16_t *__restrict__ meta,
-                                                     const uint2 *__restrict__ blo, const uint2 *__restrict__ bhi,
-                                                     const uint4 *__restrict__ bwd,
-                                                     unsigned long long *__restrict__ tcx, uint32_t epoch,
-                                                     uint32_t *__restrict__ rowstage, uint32_t *__restrict__ gbits,
-                                                     uint32_t *__restrict__ spill, uint32_t *__restrict__ ctr,
-                                                     const uint4 *__restrict__ heads, uint64_t *__restrict__ stamps)
+ * other's code (registers).  DBG: the instantiations with the per-phase
+ * stamps (tools/dyn_stamps.py) and the tests' NOPUBLISH hook, launched only
+ * when either is on: the product ones hold none of that state */
+template <bool GEN, bool DBG>
+__global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL_ROW_WAVES))) void k_dyn_row(const RowArgs a)
 {
     __shared__ RowFixed L;
     extern __shared__ uint4 rdyn[];
+    const DynGeom &g = a.g;
     /* debug: realtime at entry and after each phase (tools/dyn_stamps.py) */
     /* (straight to the slot: an array of the six stamps was kept in scratch
      * memory, zeroed by every thread) */
+    uint64_t *const stamps = DBG ? a.stamps : nullptr;
     const uint64_t t_entry = stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
     const int r = blockIdx.x, t = threadIdx.x, T = blockDim.x, lane = t & 63, wave = t >> 6, nwv = T >> 6;
     int f = blockIdx.y, s = blockIdx.z;
+    const int ld_fr = a.ld_fr;
     if (GEN) {                          /* grid (h, record slots): the frames k_dyn_rows listed */
+        const uint32_t *ctr = a.ctr;
         const uint32_t j = blockIdx.y, n = min(__builtin_amdgcn_readfirstlane(ctr[1]), g.gen_cap);
         if (j >= n) return;
         const uint32_t q = __builtin_amdgcn_readfirstlane(ctr[DYN_CTR_LIST + j]);
@@ -1490,17 +1563,16 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     }
     const size_t nb = (size_t)s * ld_fr + f;
     constexpr bool general = GEN;
-    uint64_t *const stp = stamps && t == 0
-                              ? stamps + (((size_t)s * gridDim.y + f) * g.ngroups + (max(1, (g.y0 + DYN_STATIC_ROWS - 1) /
-                                                                                        DYN_STATIC_ROWS) + r)) * 8
-                              : nullptr;
+    constexpr int SR = DYN_STATIC_ROWS;
+    uint64_t *stp = nullptr;
+    if (DBG && stamps && t == 0)
+        stp = stamps + (((size_t)s * gridDim.y + f) * g.ngroups + (max(1, (g.y0 + SR - 1) / SR) + r)) * 8;
     if (stp) stp[0] = t_entry;
     const Rect R{g.x0, g.y0, g.w, g.h};
     const int w = R.w, ndt = R.w * R.h, row = R.y0 + r, npc = NPC * w, ntask = 24 * w;
-    const int ng = g.ngroups;
-    constexpr int SR = DYN_STATIC_ROWS;
     const int nA = max(1, (R.y0 + SR - 1) / SR);
-    const DevStream *S = st + s;
+    const DevStream *S = a.st + s;
+    const uint32_t *const rows = a.rows;
     const int mbw = g.pw / 16;
     const uint32_t ysz = (uint32_t)g.pw * (uint32_t)g.ph, csz = ysz / 4;
     const int L0 = row_chroma0(w), nl = 16 * w, ntv = L0 + 8 * w;
@@ -1511,8 +1583,8 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         const int v0 = q * T + wv0;
         return v0 < nl ? 0 : (v0 < ntv ? 1 : 2);
     };
-    const __amdgpu_buffer_rsrc_t fs = buf_rsrc(src + (size_t)s * g.src_ld + (size_t)f * g.src_fr, (uint32_t)g.src_fr);
-    const __amdgpu_buffer_rsrc_t rb = buf_rsrc(refs + (size_t)s * g.ref_ld, 3u * ysz);
+    const __amdgpu_buffer_rsrc_t fs = buf_rsrc(a.src + (size_t)s * g.src_ld + (size_t)f * g.src_fr, (uint32_t)g.src_fr);
+    const __amdgpu_buffer_rsrc_t rb = buf_rsrc(a.refs + (size_t)s * g.ref_ld, 3u * ysz);
     /* pass 0's pixel loads go out first, their offsets from k_dyn_rows' row
      * table in global memory: they need neither the frame's DynFrame nor the
      * LDS copy of the table (a frame this instantiation does not code reads
@@ -1536,7 +1608,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             fetch_pass9(fo, 0u, (uint32_t)(8 * w), fs, rb, nx);
         }
     }
-    const DynFrame df = dfr[nb];
+    const DynFrame df = a.dfr[nb];
     if (df.nal < 0 || ((df.err & DF_GENERAL) != 0) != GEN) return;
 
     uint4 *lv = rdyn;
@@ -1547,16 +1619,16 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     uint32_t *mbits = reinterpret_cast<uint32_t *>(ta);   /* phase 4 on: ta is dead after phase 3 */
 
     if (t < 8) {
-        L.wo[t] = pend[s].wo[t];
-        L.wl[t] = pend[s].wl[t];
-        L.wv[t] = pend[s].wv[t];
+        L.wo[t] = a.pend[s].wo[t];
+        L.wl[t] = a.pend[s].wl[t];
+        L.wv[t] = a.pend[s].wv[t];
     }
     if (t == 0) {
         L.head_over = 0;
         L.ncand = 0;
     }
     if (t < 12) {                       /* the NAL's MB-head classes (k_dyn_rows) */
-        const uint4 *hv = heads + nb * DYN_HEAD_VECS;
+        const uint4 *hv = a.heads + nb * DYN_HEAD_VECS;
         const uint4 m = hv[t];
         const uint32_t hl = reinterpret_cast<const uint32_t *>(hv + 12)[t];
         L.hhi[t] = (uint64_t)m.x << 32 | m.y;
@@ -1570,7 +1642,12 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     for (int i = t; i < LVT_N / 2; i += T)      /* 8-byte aligned in LDS */
         reinterpret_cast<uint2 *>(L.lvt)[i] = reinterpret_cast<const uint2 *>(&g_lvt)[i];
     if (!general && t < 32) L.rt[t] = rows[nb * (size_t)(32 * g.h) + (t < 16 ? 16 * r + t : 16 * g.h + (t < 24 ? 8 * r + t - 16 : 8 * g.h + 8 * r + t - 24))];
-    const NalDesc d = nal[(size_t)s * ld_nal + df.nal];
+    /* all the MB heads need of the NAL past this point: which of the 12 head
+     * classes an MB takes (HeadSel).  The NAL's full context (NalCtx /
+     * HeadCtx: ten more uniform values) is built again, from the argument
+     * segment and the LDS waypoint table, only by the rare head over 128
+     * bits (head_slow below) */
+    const HeadSel HS = head_sel(S, a.nal[(size_t)s * a.ld_nal + df.nal]);
 
     /* ---- 1-2: records (levels -> CAVLC bodies) into LDS ---------------- */
     __syncthreads();                                    /* the row table (rt) */
@@ -1687,8 +1764,11 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         if (stp) stp[1] = __builtin_amdgcn_s_memrealtime();
         /* the row's bottom TotalCoeffs (luma 12-15, chroma AC raster 2, 3 of
          * each plane) for the row below: one granule per MB */
-        const bool nopub = (g.debug & SCROLL_DEBUG_DYN_NOPUBLISH) && s == 0 && f == 0 && r == 0;   /* tests */
+        const bool nopub = DBG && (g.debug & SCROLL_DEBUG_DYN_NOPUBLISH) && s == 0 && f == 0 && r == 0;   /* tests */
         if (t < w && r + 1 < R.h && !nopub) {
+            const KargPtr K = kargs_here();
+            unsigned long long *const tcx = row_arg(K, tcx);
+            const uint32_t epoch = row_arg(K, epoch);
             const uint16_t *mk = mt + t * NPC;
             uint64_t v = 0;
 #pragma unroll
@@ -1770,8 +1850,8 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         /* general path: records of k_dyn_code_general */
         const int q0 = r * w;
         const size_t gs = df.rbsp_bytes;                /* its record slot (k_dyn_rows) */
-        const uint16_t *M = meta + gs * (size_t)(NPC * ndt);
-        const uint2 *BL = blo + gs * (size_t)(NPC * ndt), *BH = bhi + gs * (size_t)(NPC * ndt);
+        const uint16_t *M = a.meta + gs * (size_t)(NPC * ndt);
+        const uint2 *BL = a.blo + gs * (size_t)(NPC * ndt), *BH = a.bhi + gs * (size_t)(NPC * ndt);
         for (int i = t; i < npc; i += T) {
             const int k = div_npc(i), pc = i - k * NPC;
             const int rec = rec_of(q0 + k, pc, ndt);
@@ -1800,6 +1880,9 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
      * bounded: past HANDOFF_TICKS the frame fails (DF_HANDOFF) and the row
      * finishes on zeros, so a missing granule costs one stream, not the GPU */
     if (!general && wave == nwv - 1) {
+        const KargPtr K = kargs_here();
+        const unsigned long long *const tcx = row_arg(K, tcx);
+        const uint32_t epoch = row_arg(K, epoch);
         /* waited time = the sum of the gaps between consecutive polls, a gap
          * over HANDOFF_GAP (the queue preempted or time-sliced: the row above
          * was paused too) not counted -- a slow-but-alive row above never
@@ -1827,16 +1910,14 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
 #pragma unroll
             for (int e = 0; e < 8; ++e) ta[8 * k + e] = (uint8_t)((v >> (5 * e)) & 31u);
         }
-        if (__builtin_amdgcn_ballot_w64(late) != 0 && lane == 0) atomicOr(&dfr[nb].err, DF_HANDOFF);
+        if (__builtin_amdgcn_ballot_w64(late) != 0 && lane == 0) atomicOr(&row_arg(K, dfr)[nb].err, DF_HANDOFF);
     }
-    const NalCtx c = nal_ctx(S, d, L.wo, L.wl, L.wv);
-    const HeadCtx H = head_ctx(c);
     /* a piece's levels past 8 (16-bit records of the general path below
      * QP_MIN), nullptr for the int8 forms */
     const bool wide = GEN && __builtin_amdgcn_readfirstlane(S->dyn_qp) < QP_MIN;
     auto ovf_wide = [&](int k, int pc) -> const uint4 * {
         if (!wide) return nullptr;
-        return bwd + (size_t)df.rbsp_bytes * (size_t)(NPC * ndt) + rec_of(r * w + k, pc, ndt);
+        return a.bwd + (size_t)df.rbsp_bytes * (size_t)(NPC * ndt) + rec_of(r * w + k, pc, ndt);
     };
     __syncthreads();                                    /* records, top TotalCoeffs, waypoint table */
     if (stp) stp[2] = __builtin_amdgcn_s_memrealtime();
@@ -1892,10 +1973,17 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     __syncthreads();
     if (stp) stp[3] = __builtin_amdgcn_s_memrealtime();
     const bool head_over = L.head_over;
+    /* rare (a head over 128 bits has no class form): the NAL's HeadCtx again */
+    auto head_slow = [&]() -> HeadCtx {
+        const KargPtr K = kargs_here();
+        const int nalj = row_arg(K, dfr)[nb].nal;
+        const NalDesc d = row_arg(K, nal)[(size_t)s * row_arg(K, ld_nal) + nalj];
+        return head_ctx(nal_ctx(row_arg(K, st) + s, d, L.wo, L.wl, L.wv));
+    };
     auto head_bits = [&](int rr, int col) -> uint32_t {
-        if (!head_over) return L.hlen[H.sel(rr, col)];
+        if (!head_over) return L.hlen[HS.sel(rr, col)];
         CountSink cn{0};
-        H.put_slow(cn, rr, col);
+        head_slow().put_slow(cn, rr, col);
         return cn.n;
     };
 
@@ -2004,32 +2092,41 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     }
     if (stp) stp[4] = __builtin_amdgcn_s_memrealtime();
     const uint32_t bits = colpos(mbw);
-    if (t == 0) gbits[nb * (size_t)ng + gi] = bits;
+    /* phase 5's own arguments, read here: no register held them (or a lane,
+     * written and read back) through phases 1-4 */
+    const KargPtr K5 = kargs_here();
+    uint32_t *const rowstage = row_arg(K5, rowstage), *const gbits = row_arg(K5, gbits);
+    const uint32_t rs_static_words = row_arg(K5, g.rs_static_words), rs_row_words = row_arg(K5, g.rs_row_words);
+    const uint64_t rs_frame_words = row_arg(K5, g.rs_frame_words);
+    if (t == 0) gbits[nb * (size_t)row_arg(K5, g.ngroups) + gi] = bits;
 
     /* ---- 5: bits -> the row's own row-stage words ------------------------ */
     const bool wwin = row_wide_win(w);
     uint32_t *const wb = wwin ? reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(rdyn) + row_wide_off(w)) : L.buf;
     const uint32_t GBW = wwin ? (uint32_t)ROW_GB_WIDE : (uint32_t)ROW_GB;
-    uint32_t *out = rowstage + nb * g.rs_frame_words + rs_group_words(g, nA, gi);
-    uint32_t epc = g.rs_row_words - EPC_ROW;            /* the EP-candidate record in the slot */
+    /* rs_group_words of a rect row's group */
+    uint32_t *out = rowstage + nb * rs_frame_words + ((uint64_t)nA * rs_static_words + (uint64_t)r * rs_row_words);
+    uint32_t epc = rs_row_words - EPC_ROW;              /* the EP-candidate record in the slot */
     bool lost = false;                                  /* no spill slot: the frame fails (DF_OVER) */
     if (((bits + 31u) >> 5) > epc) {
         /* the row outgrew its slot (sized for typical rows):
          * its bits go to a spill slot at the provable bound; the slot's
          * record word names it (k_dyn_epfix / the readers' rs_table follow) */
-        if (t == 0) L.spill = atomicAdd(&ctr[0], 1u);
+        const KargPtr K = kargs_here();                 /* rare: the spill pool's arguments */
+        const uint32_t rs_spill_words = row_arg(K, g.rs_spill_words);
+        if (t == 0) L.spill = atomicAdd(&row_arg(K, ctr)[0], 1u);
         __syncthreads();
         const uint32_t k = L.spill;
-        uint32_t *fr = rowstage + nb * g.rs_frame_words;
-        uint32_t *sp = spill + (size_t)k * g.rs_spill_words;
+        uint32_t *fr = rowstage + nb * rs_frame_words;
+        uint32_t *sp = row_arg(K, spill) + (size_t)k * rs_spill_words;
         /* none left, or out of the readers' reach (32-bit byte offsets from fr) */
-        if (k >= g.rs_spill_cap || (uint64_t)(sp - fr) + g.rs_spill_words > 0x3fffffffull) {
-            if (t == 0) atomicOr(&dfr[nb].err, DF_OVER);
+        if (k >= row_arg(K, g.rs_spill_cap) || (uint64_t)(sp - fr) + rs_spill_words > 0x3fffffffull) {
+            if (t == 0) atomicOr(&row_arg(K, dfr)[nb].err, DF_OVER);
             lost = true;
         } else {
             if (t == 0) out[epc] = 0x80000000u | (uint32_t)(sp - fr);
             out = sp;
-            epc = g.rs_spill_words - EPC_ROW;
+            epc = rs_spill_words - EPC_ROW;
         }
     }
     const uint32_t nw = lost ? 0u : min((bits + 31u) >> 5, epc);     /* provable bound: never clipped */
@@ -2050,7 +2147,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             const int k = col - R.x0;
             const bool in = k >= 0 && k < w;
             if (one && !head_over) {
-                const int cls = H.sel(row, col);
+                const int cls = HS.sel(row, col);
                 const uint32_t hl = L.hlen[cls];
                 uint32_t tv = 1u, tn = 1u;                      /* coded_block_pattern ue(0) */
                 if (in) {
@@ -2076,10 +2173,10 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             WSink sk{win, 0, 0, 0};
             sk.start(pos);
             if (!head_over) {
-                const int cls = H.sel(row, col);
+                const int cls = HS.sel(row, col);
                 sk.put_cap(cap_of_msb(L.hhi[cls], L.hlo[cls], L.hlen[cls]));
             } else {
-                H.put_slow(sk, row, col);
+                head_slow().put_slow(sk, row, col);
             }
             if (!in) {
                 sk.put(1, 1);                           /* coded_block_pattern ue(0) */
@@ -2111,7 +2208,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
                     else put_piece(wb, p0, n, pos, tv, tl, bd, mv & 255u);
                 }
             } else {
-                ovf_put(wb, p0, n, pos, PT, TB, bd, ovf_wide(k, pc), pc, nC);
+                ovf_put((LdsWords)wb, p0, n, pos, PT, TB, bd, ovf_wide(k, pc), pc, nC);
             }
         }
         __syncthreads();
@@ -3728,29 +3825,53 @@ int dyn_launch_code(hipStream_t hs, int nframes, int S, DevStream *st, const Nal
                        pend, nal, ld_nal, *g, x->rows, src, refs, x->meta, x->body_lo, x->body_hi, x->body_w,
                        x->ctr);
     if (hipGetLastError() != hipSuccess) return -1;
+    /* the debug instantiations only with the stamps or the tests' NOPUBLISH hook on */
+    const bool dbg = stamps || (g->debug & SCROLL_DEBUG_DYN_NOPUBLISH);
+    void (*const krow)(RowArgs) = dbg ? &k_dyn_row<false, true> : &k_dyn_row<false, false>;
+    void (*const kgen)(RowArgs) = dbg ? &k_dyn_row<true, true> : &k_dyn_row<true, false>;
     if (row_lds_bytes(g->w) > 65536) {
         /* wide rects (a whole 1280- or 4096-px row): dynamic LDS past the
          * 64 KB default, up to the CU's 160 KB (set_dyn_rect's bound) */
         const int rl = (int)row_lds_bytes(g->w);
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dyn_row<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, rl) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dyn_row<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, rl) != hipSuccess)
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(krow), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                rl) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void *>(kgen), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                rl) != hipSuccess)
             return -1;
     }
+    /* every launch passes its own copy in its own argument segment: pool
+     * growth, set_dyn_rect, a QP change or a second batch on another stream
+     * change nothing a launch in flight reads */
+    RowArgs ra{};
+    ra.st = st;
+    ra.nal = nal;
+    ra.pend = pend;
+    ra.dfr = dfr;
+    ra.rows = x->rows;
+    ra.src = src;
+    ra.refs = refs;
+    ra.heads = x->heads;
+    ra.ld_nal = ld_nal;
+    ra.ld_fr = ld_fr;
+    ra.g = *g;
+    ra.tcx = x->tcx;
+    ra.epoch = epoch;
+    ra.rowstage = x->rowstage;
+    ra.gbits = x->gbits;
+    ra.spill = x->spill;
+    ra.ctr = x->ctr;
+    ra.meta = x->meta;
+    ra.blo = x->body_lo;
+    ra.bhi = x->body_hi;
+    ra.bwd = x->body_w;
+    ra.stamps = stamps;
     if (ev0 && hipEventRecord(ev0, hs) != hipSuccess) return -1;
-    hipLaunchKernelGGL(k_dyn_row<false>, dim3(g->h, nframes, S), dim3(row_threads(g->w)),
-                       row_lds_bytes(g->w), hs, st, nal, ld_nal, pend, dfr, ld_fr, *g, x->rows, src, refs,
-                       x->meta, x->body_lo, x->body_hi, x->body_w, x->tcx, epoch, x->rowstage, x->gbits, x->spill,
-                       x->ctr, x->heads, stamps);
+    hipLaunchKernelGGL(krow, dim3(g->h, nframes, S), dim3(row_threads(g->w)), row_lds_bytes(g->w), hs, ra);
     if (hipGetLastError() != hipSuccess) return -1;
     if (ev1 && hipEventRecord(ev1, hs) != hipSuccess) return -1;
     /* the general path: one row workgroup per record slot that may be taken */
-    hipLaunchKernelGGL(k_dyn_row<true>, dim3(g->h, std::min<uint32_t>(g->gen_cap, (uint32_t)(nframes * S)), 1),
-                       dim3(row_threads(g->w)),
-                       row_lds_bytes(g->w), hg, st, nal, ld_nal, pend, dfr, ld_fr, *g, x->rows, src, refs,
-                       x->meta, x->body_lo, x->body_hi, x->body_w, x->tcx, epoch, x->rowstage, x->gbits, x->spill,
-                       x->ctr, x->heads, stamps);
+    hipLaunchKernelGGL(kgen, dim3(g->h, std::min<uint32_t>(g->gen_cap, (uint32_t)(nframes * S)), 1),
+                       dim3(row_threads(g->w)), row_lds_bytes(g->w), hg, ra);
     if (hipGetLastError() != hipSuccess) return -1;
     if (fk) {                           /* the static row groups beside the block coder too */
         if (dyn_launch_static(hg, nframes, S, st, nal, ld_nal, pend, dfr, ld_fr, g, x) ||
@@ -3873,7 +3994,7 @@ extern "C" int scroll_debug_row_occupancy(int w, int mbw, int extra_lds)
     int n = -1;
     (void)mbw;                              /* (round 4's LDS grew with the picture width) */
     const size_t lds = (size_t)((long)row_lds_bytes(w) + extra_lds);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(&k_dyn_row<false>),
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(&k_dyn_row<false, false>),
                                                      row_threads(w), lds) != hipSuccess)
         return -1;
     return n;
