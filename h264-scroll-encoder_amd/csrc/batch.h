@@ -3,6 +3,7 @@
  * include/composer_batch.h: the batch's state and what its files share.
  *   batch_core.hip    create / destroy, streams, compose, sync, output, timing
  *   batch_dyn.hip     the dynamic rect, its reconstruction and its QP probe
+ *   batch_rate.hip    the plain rect's per-frame QP table and the pick on the device
  *   batch_hint.hip    UI hints, the rect under hints, the splice
  *   batch_ingest.hip  ingest, I_PCM files, reference updates
  *   batch_dropin.hip  the synchronous drop-in helpers of engine.h
@@ -22,6 +23,7 @@
 #include "dyn_engine.h"         /* DynScratch, DynFork */
 #include "splice_engine.h"      /* SpliceFrame, SpliceMbRec, SpliceUnit */
 #include "ingest_engine.h"      /* IngestFile, IngestScan, IngestOut */
+#include "pick_engine.h"        /* PickOut */
 
 /* (set_err: scroll::batch's, below) */
 #define HIPCHK(x)                                                                  \
@@ -102,10 +104,23 @@ struct ScrollBatch {
         uint8_t *cls = nullptr;         /* [max_streams * max_frames]: k_hprobe_class (scroll_batch_dyn_probe_hinted) */
         int hinted = 0;                 /* the last probe was the hinted one */
         int nframes = -1, nstreams = 0, nq = 0;   /* the last probe; nframes -1: none */
+        uint8_t qps[SCROLL_DYN_PROBE_MAX_QPS] = {};   /* its candidates (scroll_batch_dyn_pick) */
         hipEvent_t fin = nullptr;       /* recorded after the last probe's launches */
         hipEvent_t ev[2] = {};          /* timing: around them (created on first use) */
         int timed = 0;
     } pb;
+    /* the plain rect's per-frame QP table (dx.qpf, batch_rate.hip) and the
+     * pick that fills it from the probe on the device (pick_kernels.hip);
+     * everything allocated on first use, freed with the rect */
+    std::vector<uint8_t> h_qpf;         /* the table as the host last knew it, [max_streams * max_frames] */
+    int qpf_dev = 0;                    /* the device may have written it since (a pick, a caller's kernel) */
+    struct Rate {
+        long long *level = nullptr;     /* [max_streams]: the buckets' levels */
+        uint32_t *fb = nullptr;         /* [max_streams]: frame_bits per stream of the last pick that gave them */
+        PickOut *out = nullptr;         /* [max_streams * max_frames]: the last pick's choices */
+        hipEvent_t fin = nullptr;       /* recorded after the last pick's launch */
+        int nframes = -1, nstreams = 0; /* the last pick; nframes -1: none */
+    } rt;
     /* UI hints: staged like the dynamic rect (shares
      * d_dfr, d_stage and geo.slot_bytes; the two are exclusive) */
     int hint_on = 0;
@@ -214,6 +229,13 @@ int load_nals(ScrollBatch *b);
 void probe_release(ScrollBatch *b);
 void dyn_release(ScrollBatch *b);
 int dyn_grow_pools(ScrollBatch *b);
+int dyn_reserve_gen(ScrollBatch *b, size_t need);
+
+/* ---- batch_rate.hip ---- */
+void rate_release(ScrollBatch *b);
+/* *any: some entry of the per-frame QP table differs from 0xFF (reads the
+ * table back when the device may have written it) */
+int qp_frames_any(ScrollBatch *b, bool *any);
 
 /* ---- batch_hint.hip ---- */
 int hint_upload(ScrollBatch *b);

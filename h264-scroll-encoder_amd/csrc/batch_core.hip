@@ -538,6 +538,8 @@ void scroll_batch_destroy(ScrollBatch *b)
     for (hipEvent_t e : b->rc_ev)
         if (e) (void)hipEventDestroy(e);
     probe_release(b);
+    (void)hipFree(b->dx.qpf);
+    rate_release(b);
     (void)hipFree(b->d_hf);
     (void)hipFree(b->d_pool);
     (void)hipFree(b->d_spf);
@@ -646,6 +648,9 @@ int scroll_batch_set_config(ScrollBatch *b, int s, const ComposerConfig *cfg)
             const int q = b->h_dyn_qp[i0 + f];
             bad = q >= 0 && q != 26;
         }
+        bool any = false;                /* the plain rect's per-frame table too */
+        if (!bad && b->dx.qpf && !qp_frames_any(b, &any))
+            for (size_t f = 0; !bad && f < F; ++f) bad = b->h_qpf[i0 + f] != 0xFFu && b->h_qpf[i0 + f] != 26u;
         if (bad) {
             set_err("scroll_batch_set_config: stream %d's rect QP is not 26: it cannot turn the deblocking "
                     "filter on (no deblocking_filter_control_present_flag)", s);
@@ -704,6 +709,18 @@ int scroll_batch_compose_ex(ScrollBatch *b, int nframes, void *hip_stream, int f
                     "covers the plain dynamic rect, and the rect under UI hints with "
                     "scroll_batch_set_dyn_recon_hinted, never spliced slices: clear the hints / splices, opt "
                     "in or turn it off");
+            return SCROLL_ERR_CONFIG;
+        }
+    }
+    if (b->hint_on && b->dx.qpf) {
+        /* the per-frame QP table is the plain rect's; under hints the frames' QPs are set_dyn_qp_at's */
+        bool any = false;
+        int rc = qp_frames_any(b, &any);
+        if (rc) return rc;
+        if (any) {
+            set_err("scroll_batch_compose: per-frame rect QPs are set (scroll_batch_set_dyn_qp_frames / "
+                    "scroll_batch_dyn_pick) and so are UI hints: clear one of them "
+                    "(scroll_batch_clear_dyn_qp_frames; under hints: scroll_batch_set_dyn_qp_at)");
             return SCROLL_ERR_CONFIG;
         }
     }

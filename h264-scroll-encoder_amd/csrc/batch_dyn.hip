@@ -66,6 +66,8 @@ void dyn_release(ScrollBatch *b)
     (void)hipFree(b->dx.rowstage);
     (void)hipFree(b->dx.ctr);
     (void)hipFree(b->dx.gbits);
+    (void)hipFree(b->dx.qpf);          /* the per-frame QP table, its pick and the buckets' levels */
+    rate_release(b);
     (void)hipFree(b->d_rec);           /* the reconstruction goes with the rect it was sized for */
     (void)hipFree(b->d_sse);
     b->d_rec = nullptr;
@@ -130,6 +132,42 @@ int dyn_grow_pools(ScrollBatch *b)
     b->geo.gen_cap = g.gen_cap;
     b->geo.rs_spill_cap = g.rs_spill_cap;
     b->dyn_grow = 1;
+    return SCROLL_OK;
+}
+
+/* general-path record slots for `need` NALs (at most one per frame), keeping
+ * everything else: for per-frame QPs below QP_MIN that the engine knows of
+ * before the launch (batch_rate.hip).  The batch is idle when this runs. */
+int dyn_reserve_gen(ScrollBatch *b, size_t need)
+{
+    if (!b->dyn_on) return SCROLL_OK;
+    need = std::min(need, (size_t)b->max_streams * (size_t)b->max_frames);
+    if (need <= b->geo.gen_cap) return SCROLL_OK;
+    HIPCHK(hipSetDevice(b->device));
+    const size_t nrec = need * DYN_PIECES * (size_t)b->geo.w * b->geo.h;
+    uint16_t *meta = nullptr;
+    uint2 *lo = nullptr, *hi = nullptr;
+    uint4 *wd = nullptr;
+    hipError_t e = hipMalloc(&meta, nrec * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMalloc(&lo, nrec * sizeof(uint2));
+    if (e == hipSuccess) e = hipMalloc(&hi, nrec * sizeof(uint2));
+    if (e == hipSuccess) e = hipMalloc(&wd, nrec * sizeof(uint4));
+    if (e != hipSuccess) {
+        (void)hipFree(meta);
+        (void)hipFree(lo);
+        (void)hipFree(hi);
+        (void)hipFree(wd);
+        return hip_fail("the dynamic rect's general-path record pool", e, true);
+    }
+    (void)hipFree(b->dx.meta);
+    (void)hipFree(b->dx.body_lo);
+    (void)hipFree(b->dx.body_hi);
+    (void)hipFree(b->dx.body_w);
+    b->dx.meta = meta;
+    b->dx.body_lo = lo;
+    b->dx.body_hi = hi;
+    b->dx.body_w = wd;
+    b->geo.gen_cap = (uint32_t)need;
     return SCROLL_OK;
 }
 
@@ -198,14 +236,16 @@ static int probe_args(ScrollBatch *b, const char *who, int nframes, const uint8_
  * nothing; ctr: the counters it zeroes, or none), then the probe's own
  * launches: own(hs, S, G, ev1), ev1 to record after them when timed */
 template <class Own>
-static int probe_run(ScrollBatch *b, int nframes, int nq, void *hip_stream, int hinted, uint32_t *ctr, Own own)
+static int probe_run(ScrollBatch *b, int nframes, const ProbeQps &Q, void *hip_stream, int hinted, uint32_t *ctr,
+                     Own own)
 {
     ScrollBatch::Probe &p = b->pb;
     hipStream_t hs = hip_stream ? (hipStream_t)hip_stream : b->own;
-    const int S = b->nstreams, ld_fr = b->max_frames;
+    const int S = b->nstreams, ld_fr = b->max_frames, nq = Q.n;
     p.nframes = nframes;
     p.nstreams = S;
     p.nq = nq;
+    for (int k = 0; k < nq; ++k) p.qps[k] = Q.qp[k];
     p.timed = 0;
     p.hinted = hinted;
     if (S > 0 && nframes > 0) {
@@ -552,8 +592,8 @@ int scroll_batch_set_dyn_qp_at(ScrollBatch *b, int s, int f, int qp)
 {
     if (!b || !b->hint_on || !b->dyn_on || s < 0 || s >= b->nstreams || f < 0 || f >= b->max_frames ||
         qp < -1 || qp > SCROLL_DYN_QP_MAX) {
-        set_err("scroll_batch_set_dyn_qp_at: needs UI hints and the dynamic rect; stream / frame / QP "
-                "(-1, 0..%d) out of range", SCROLL_DYN_QP_MAX);
+        set_err("scroll_batch_set_dyn_qp_at: needs UI hints and the dynamic rect (without hints: "
+                "scroll_batch_set_dyn_qp_frames); stream / frame / QP (-1, 0..%d) out of range", SCROLL_DYN_QP_MAX);
         return SCROLL_ERR_ARG;
     }
     if (qp >= 0 && qp != 26 && !b->h_st[s].deblock) {
@@ -726,10 +766,11 @@ int scroll_batch_dyn_probe(ScrollBatch *b, int nframes, const uint8_t *qps, int 
     ScrollBatch::Probe &p = b->pb;
     const int ld_fr = b->max_frames;
     /* k_dyn_rows after the state pass, into the probe's own rows / heads / ctr */
-    return probe_run(b, nframes, nq, hip_stream, 0, p.ctr, [&](hipStream_t hs, int S, DynGeom &G, hipEvent_t ev1) {
+    return probe_run(b, nframes, Q, hip_stream, 0, p.ctr, [&](hipStream_t hs, int S, DynGeom &G, hipEvent_t ev1) {
         G.gen_cap = (uint32_t)((size_t)b->max_streams * ld_fr);
+        /* (no per-frame QP table: the probe's QPs are its arguments) */
         if (dyn_launch_rows(hs, nframes, S, b->d_st, p.nal, b->ld_nal, p.pend, p.dfr, ld_fr, &G, p.rows, p.ctr,
-                            p.heads)) {
+                            p.heads, nullptr)) {
             set_err("k_dyn_rows launch: %s", hipGetErrorString(hipGetLastError()));
             return SCROLL_ERR_HIP;
         }
@@ -777,7 +818,7 @@ int scroll_batch_dyn_probe_hinted(ScrollBatch *b, int nframes, const uint8_t *qp
     }
     const int ld_fr = b->max_frames;
     /* no k_dyn_rows after the state pass (the motion is the hints'), and no counters for it to zero */
-    return probe_run(b, nframes, nq, hip_stream, 1, nullptr, [&](hipStream_t hs, int S, DynGeom &G, hipEvent_t ev1) {
+    return probe_run(b, nframes, Q, hip_stream, 1, nullptr, [&](hipStream_t hs, int S, DynGeom &G, hipEvent_t ev1) {
         if (hprobe_launch(hs, nframes, S, b->d_st, p.nal, b->ld_nal, p.pend, p.dfr, ld_fr, b->d_hf, b->d_pool,
                           b->d_spf, b->fallback, &G, b->d_src, b->d_refs, &Q, p.cls, p.res, p.done, ev1)) {
             set_err("k_hdyn_probe launch: %s", hipGetErrorString(hipGetLastError()));

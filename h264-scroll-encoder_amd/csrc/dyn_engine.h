@@ -29,6 +29,9 @@ typedef struct {
                                      * holding general record k */
     uint32_t ctr_frames;            /* frames the lists hold (S ld_fr) */
     uint32_t epoch;                 /* look-back epoch of the last compose (24 bits, never 0) */
+    uint8_t *qpf;                   /* per (stream, frame of the compose) [s ld_fr + f]: the frame's rect QP,
+                                     * 0xFF the stream's (scroll_batch_set_dyn_qp_frames, k_dyn_pick); NULL
+                                     * until first used */
 } DynScratch;
 #define DYN_HEAD_VECS 16             /* heads[] per frame: 12 classes MSB first, then their lengths */
 #define DYN_CTR_LIST 4               /* ctr[]: the lists (the counters zeroed per compose: 4 words) */
@@ -45,10 +48,13 @@ typedef struct {
  * ([1] and the list from DYN_CTR_LIST, zeroed by k_plan's state pass), the
  * frames with a row on the general path, of which g->gen_cap fit.  It writes
  * DynFrame.rbsp_bytes / ep / err of dfr and nothing else: the QP probe runs
- * it into buffers of its own */
+ * it into buffers of its own.  qpf: the per-frame QP table (DynScratch.qpf)
+ * or NULL; the frame's resolved QP goes into DynFrame.ep, where the coding
+ * kernels read it until k_dyn_epfix replaces it with the EP count (the
+ * probes pass NULL: their QPs are arguments) */
 int dyn_launch_rows(hipStream_t hs, int nframes, int S, const DevStream *st, const NalDesc *nal, int ld_nal,
                     const PlanPending *pend, DynFrame *dfr, int ld_fr, const DynGeom *g, uint32_t *rows,
-                    uint32_t *ctr, uint4 *heads);
+                    uint32_t *ctr, uint4 *heads, const uint8_t *qpf);
 /* k_dyn_rows + k_dyn_code_general (records of the general-path NALs) +
  * k_dyn_row (every rect row: block coding + packing -> its row-stage bits);
  * fk != NULL: the fork above (k_dyn_static then runs on the side stream);

@@ -300,8 +300,9 @@ __device__ inline void code_frame(const DevStream *__restrict__ st,
 
     const int ndt = g.w * g.h, ntask = 24 * ndt;
     const int task = bx * CODE_T + t;
-    /* the stream's rect QP; below QP_MIN the levels need 16 bits (wide) */
-    const int qpy = __builtin_amdgcn_readfirstlane(st[s].dyn_qp);
+    /* the frame's rect QP (k_dyn_rows: DynFrame.ep until k_dyn_epfix); below
+     * QP_MIN the levels need 16 bits (wide) */
+    const int qpy = __builtin_amdgcn_readfirstlane((int)df.ep);
     const QParams ql = qparams_rt(qpy), qc = qparams_rt(qp_chroma(qpy));
     const bool wide = qpy < QP_MIN;
     const size_t nb = (size_t)s * ld_fr + f;
@@ -823,13 +824,20 @@ __device__ inline uint4 body_msb(uint64_t hi, uint64_t lo, uint32_t n)
  *                   has a half-pel step (the general path)
  *   24 h .. 32 h    the lower bilinear row (used when the fraction != 0)
  * Sets DynFrame.err = DF_GENERAL when some row of the NAL needs the general
- * path (never for waypoints the composer creates), else 0. */
+ * path (never for waypoints the composer creates), else 0.
+ * Resolves the frame's rect QP, once for every kernel after it: entry
+ * [s ld_fr + f] of the per-frame table qpf (scroll_batch_set_dyn_qp_frames,
+ * k_dyn_pick; NULL: no table; 0xFF or anything above 51: no entry), else the
+ * stream's.  It travels in DynFrame.ep, which is free until k_dyn_epfix puts
+ * the EP count there: k_dyn_code_general, k_dyn_row, k_dyn_recon and
+ * k_dyn_static all run between the two and read it with the DynFrame they
+ * load anyway. */
 __global__ __launch_bounds__(256) void k_dyn_rows(const DevStream *__restrict__ st,
                                                   const NalDesc *__restrict__ nal, int ld_nal,
                                                   const PlanPending *__restrict__ pend,
                                                   DynFrame *__restrict__ dfr, int ld_fr, DynGeom g,
                                                   uint32_t *__restrict__ rows, uint32_t *__restrict__ ctr,
-                                                  uint4 *__restrict__ heads)
+                                                  uint4 *__restrict__ heads, const uint8_t *__restrict__ qpf)
 {
     __shared__ int32_t wo[8], wl[8], wv[8];
     __shared__ int32_t gen;
@@ -889,7 +897,9 @@ __global__ __launch_bounds__(256) void k_dyn_rows(const DevStream *__restrict__ 
         }
         rw[i] = e;
     }
-    if (my_gen || S->dyn_qp < QP_MIN) gen = 1;            /* half-pel chroma chains; 16-bit levels */
+    const uint32_t qe = qpf ? qpf[(size_t)s * ld_fr + f] : 0xFFu;
+    const int qpy = qe <= 51u ? (int)qe : S->dyn_qp;      /* the frame's own, else the stream's */
+    if (my_gen || qpy < QP_MIN) gen = 1;                  /* half-pel chroma chains; 16-bit levels */
     __syncthreads();
     if (t == 0) {
         /* a general-path NAL takes a record slot (index in rbsp_bytes until
@@ -907,7 +917,7 @@ __global__ __launch_bounds__(256) void k_dyn_rows(const DevStream *__restrict__ 
             }
         }
         DF->err = e;
-        DF->ep = 0u;                                    /* k_dyn_epfix sets it */
+        DF->ep = (uint32_t)qpy;                         /* the frame's QP, until k_dyn_epfix sets the EP count */
     }
 }
 
@@ -951,7 +961,8 @@ __global__ __launch_bounds__(GW) void k_dyn_static(const DevStream *__restrict__
     const int gi = (int)blockIdx.x >= nA ? (int)blockIdx.x + R.h : (int)blockIdx.x;
     const int ng = g.ngroups, f = blockIdx.y, s = blockIdx.z, t = threadIdx.x;
     const size_t nb = (size_t)s * ld_fr + f;
-    const int j = dfr[nb].nal;
+    const DynFrame df = dfr[nb];
+    const int j = df.nal;
     if (j < 0) return;
     const bool first = gi == 0, last = gi == ng - 1;
     if (t < 8) {
@@ -967,7 +978,7 @@ __global__ __launch_bounds__(GW) void k_dyn_static(const DevStream *__restrict__
     const NalDesc d = nal[(size_t)s * ld_nal + j];
     wave_sync();
     NalCtx c = nal_ctx(S, d, L.wo, L.wl, L.wv);
-    c.qpd = S->dyn_qp - QP_DEFAULT;                     /* the stream's rect QP: slice_qp_delta */
+    c.qpd = (int)df.ep - QP_DEFAULT;                    /* the frame's rect QP (k_dyn_rows): slice_qp_delta */
     const HeadCtx H = head_ctx(c);
     const int mbw = H.mbw, mbh = c.h / 16;
     int ra, rb;
@@ -1657,8 +1668,8 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
          * one mv): 0 or 4 here (k_dyn_rows sends half-pel chains to the
          * general path) */
         const uint32_t frc = __builtin_amdgcn_readfirstlane((L.rt[16] >> 28) & 7u);
-        /* the stream's rect QP (QP_MIN and up here: int8 levels) */
-        const int qpy = __builtin_amdgcn_readfirstlane(S->dyn_qp);
+        /* the frame's rect QP (k_dyn_rows; QP_MIN and up here: int8 levels) */
+        const int qpy = __builtin_amdgcn_readfirstlane((int)df.ep);
         const QParams ql = g_qptab.q[qpy].l, qc = g_qptab.q[qpy].c;
         /* round 6: a wave's passes are luma ones, then chroma ones, then
          * none (L0 and T are multiples of 64), so two loops whose kind is
@@ -1914,7 +1925,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     }
     /* a piece's levels past 8 (16-bit records of the general path below
      * QP_MIN), nullptr for the int8 forms */
-    const bool wide = GEN && __builtin_amdgcn_readfirstlane(S->dyn_qp) < QP_MIN;
+    const bool wide = GEN && __builtin_amdgcn_readfirstlane((int)df.ep) < QP_MIN;
     auto ovf_wide = [&](int k, int pc) -> const uint4 * {
         if (!wide) return nullptr;
         return a.bwd + (size_t)df.rbsp_bytes * (size_t)(NPC * ndt) + rec_of(r * w + k, pc, ndt);
@@ -3787,11 +3798,11 @@ __global__ __launch_bounds__(256) void k_dyn_synth(uint8_t *__restrict__ src, Dy
 /* ---------------------------------------------------------------------- */
 int dyn_launch_rows(hipStream_t hs, int nframes, int S, const DevStream *st, const NalDesc *nal, int ld_nal,
                     const PlanPending *pend, DynFrame *dfr, int ld_fr, const DynGeom *g, uint32_t *rows,
-                    uint32_t *ctr, uint4 *heads)
+                    uint32_t *ctr, uint4 *heads, const uint8_t *qpf)
 {
     if (nframes <= 0 || S <= 0) return 0;
     hipLaunchKernelGGL(k_dyn_rows, dim3(nframes, S), dim3(256), 0, hs, st, nal, ld_nal, pend, dfr, ld_fr,
-                       *g, rows, ctr, heads);
+                       *g, rows, ctr, heads, qpf);
     return hipGetLastError() != hipSuccess ? -1 : 0;
 }
 
@@ -3813,7 +3824,8 @@ int dyn_launch_code(hipStream_t hs, int nframes, int S, DevStream *st, const Nal
             ready |= 1ull << dev;
         }
     }
-    if (dyn_launch_rows(hs, nframes, S, st, nal, ld_nal, pend, dfr, ld_fr, g, x->rows, x->ctr, x->heads)) return -1;
+    if (dyn_launch_rows(hs, nframes, S, st, nal, ld_nal, pend, dfr, ld_fr, g, x->rows, x->ctr, x->heads, x->qpf))
+        return -1;
     hipStream_t hg = hs;                /* the general path's stream */
     if (fk) {
         if (hipEventRecord(fk->e0, hs) != hipSuccess || hipStreamWaitEvent(fk->side, fk->e0, 0) != hipSuccess)

@@ -6,7 +6,7 @@
  *
  * k_dyn_recon repeats the coder's forward half per 4x4 block with the
  * coder's own functions (dyn_device.h: fwd4x4, quant, quant_dc at the
- * stream's QP / QPc), so its levels are the coded ones, and runs the
+ * frame's QP / QPc), so its levels are the coded ones, and runs the
  * decoder's half on them (recon_device.h).  It reads k_dyn_rows' prediction
  * rows and is independent of k_dyn_row: levels stay in 32-bit registers, so
  * the same code serves the int8 path and the general path (QP < 22); rows
@@ -86,7 +86,8 @@ __global__ __launch_bounds__(RC_T) void k_dyn_recon(const DevStream *__restrict_
     const uint8_t *rb = refs + (size_t)s * g.ref_ld;
     const RowPred<GEN> P{L, rb, (uint32_t)g.pw * (uint32_t)g.ph / 4, g.x0, g.y0 + r, st + s,
                          nal + (size_t)s * ld_nal + df.nal};
-    recon_row<RC_T>(P, __builtin_amdgcn_readfirstlane(st[s].dyn_qp), g, r,
+    /* the frame's rect QP: k_dyn_rows left it in DynFrame.ep (k_dyn_epfix runs after this kernel) */
+    recon_row<RC_T>(P, __builtin_amdgcn_readfirstlane((int)df.ep), g, r,
                     (size_t)s * g.src_ld + (size_t)f * g.src_fr, src, rec, L.red, sse + nb * 3);
 }
 

@@ -133,6 +133,14 @@ class ScrollDynProbe(ctypes.Structure):
     _fields_ = [("sse", ctypes.c_uint64 * 3), ("bits", ctypes.c_uint32), ("nonzero", ctypes.c_uint32)]
 
 
+SCROLL_DYN_RATE_FRAME, SCROLL_DYN_RATE_BUCKET = 0, 1
+
+
+class ScrollDynRate(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_uint32), ("frame_bits", ctypes.c_uint32), ("bucket_bits", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} not built: run `make -C h264-scroll-encoder_amd` "
@@ -218,6 +226,18 @@ def _load():
         "scroll_batch_dyn_probe_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t),
                                                             P(ctypes.c_size_t)]),
         "scroll_batch_dyn_probe_ms": (ctypes.c_float, [ctypes.c_void_p]),
+        "scroll_batch_set_dyn_qp_frames": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                          P(ctypes.c_int8)]),
+        "scroll_batch_clear_dyn_qp_frames": (ctypes.c_int, [ctypes.c_void_p]),
+        "scroll_batch_dyn_qp_frames": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      P(ctypes.c_int8)]),
+        "scroll_batch_dyn_qp_frames_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t)]),
+        "scroll_batch_dyn_pick": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, P(ScrollDynRate),
+                                                 P(ctypes.c_uint32), ctypes.c_void_p]),
+        "scroll_batch_dyn_pick_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                        P(ctypes.c_int), P(ctypes.c_int)]),
+        "scroll_batch_dyn_rate_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, P(ctypes.c_int64),
+                                                       ctypes.c_int]),
         "scroll_batch_kernel_stats_ex": (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_double),
                                                         P(ctypes.c_int)]),
         "scroll_batch_set_hints": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
@@ -798,6 +818,86 @@ class Batch:
         """with enable_timing: HIP-event ms of the last probe's launches (-1
         without)"""
         return lib.scroll_batch_dyn_probe_ms(self.h)
+
+    # ---- the plain rect at a QP of its own per frame ----
+    def set_dyn_qp_frames(self, qps, stream=None, f0=0):
+        """frame f of every following compose of the plain dynamic rect codes
+        at qps[..., f - f0] (-1: the stream's QP): an [S][F] array, one row per
+        stream, or an [F] array for stream `stream` (None: every stream)
+        (scroll_batch_set_dyn_qp_frames)"""
+        import numpy as np
+        q = np.ascontiguousarray(np.clip(np.asarray(qps, dtype=np.int64), -128, 127).astype(np.int8))
+        if q.ndim == 2:
+            if stream is not None:
+                raise ValueError("set_dyn_qp_frames: an [S][F] array names its streams itself")
+            rows = list(enumerate(q))
+        elif q.ndim == 1:
+            rows = [(-1 if stream is None else stream, q)]
+        else:
+            raise ValueError("set_dyn_qp_frames: an [S][F] or [F] array")
+        for s, row in rows:
+            row = np.ascontiguousarray(row)
+            self._chk(lib.scroll_batch_set_dyn_qp_frames(self.h, s, f0, len(row),
+                                                         row.ctypes.data_as(ctypes.POINTER(ctypes.c_int8))),
+                      "set_dyn_qp_frames")
+
+    def clear_dyn_qp_frames(self):
+        self._chk(lib.scroll_batch_clear_dyn_qp_frames(self.h), "clear_dyn_qp_frames")
+
+    def dyn_qp_frames(self, nframes):
+        """the per-frame QP table as it stands on the device, int8 [S][nframes],
+        -1: the stream's QP (synchronises: how dyn_pick's choices are learnt)"""
+        import numpy as np
+        out = np.full((self.num_streams, nframes), -1, dtype=np.int8)
+        for s in range(out.shape[0]):
+            self._chk(lib.scroll_batch_dyn_qp_frames(self.h, s, 0, nframes,
+                                                     out[s].ctypes.data_as(ctypes.POINTER(ctypes.c_int8))),
+                      "dyn_qp_frames")
+        return out
+
+    def dyn_qp_frames_device(self):
+        """(device pointer, stream stride) of the per-frame QP table, one byte
+        per frame, 0xFF: the stream's QP"""
+        ls = ctypes.c_size_t()
+        p = lib.scroll_batch_dyn_qp_frames_device(self.h, ctypes.byref(ls))
+        return p, ls.value
+
+    def dyn_pick(self, nframes, frame_bits, bucket_bits=None, per_stream=None, stream=None):
+        """the per-frame QPs of the next compose(nframes), picked on the device
+        from the last dyn_probe (scroll_batch_dyn_pick): per frame the
+        candidate of the smallest squared error whose cost bits + len(se(qp -
+        26)) fits frame_bits, or with bucket_bits a leaky bucket per stream
+        that frame_bits refills; per_stream: frame_bits of every stream.
+        Returns (k[S][F], qp[S][F], status[S][F]), int32: status 0 chosen, 1
+        the cheapest taken over budget, 2 nothing chosen (k, qp -1: the frame
+        keeps the stream's QP), SCROLL_ERR_DEVICE for a frame the probe did
+        not finish.  `stream`: the HIP stream of the probe and the compose"""
+        import numpy as np
+        rate = ScrollDynRate(SCROLL_DYN_RATE_FRAME if bucket_bits is None else SCROLL_DYN_RATE_BUCKET,
+                             int(frame_bits), 0 if bucket_bits is None else int(bucket_bits), 0)
+        fb = None
+        if per_stream is not None:
+            fb = (ctypes.c_uint32 * self.num_streams)(*[int(v) for v in per_stream])
+        self._chk(lib.scroll_batch_dyn_pick(self.h, nframes, ctypes.byref(rate), fb, stream), "dyn_pick")
+        S = self.num_streams
+        k = np.full((S, nframes), -1, np.int32)
+        qp = np.full((S, nframes), -1, np.int32)
+        st = np.zeros((S, nframes), np.int32)
+        a, c = ctypes.c_int(), ctypes.c_int()
+        for s in range(S):
+            for f in range(nframes):
+                rc = lib.scroll_batch_dyn_pick_result(self.h, s, f, ctypes.byref(a), ctypes.byref(c))
+                if rc < 0 and rc != SCROLL_ERR_DEVICE:
+                    self._chk(rc, "dyn_pick_result")
+                k[s, f], qp[s, f], st[s, f] = a.value, c.value, rc
+        return k, qp, st
+
+    def dyn_rate_level(self, s, set=None):
+        """stream s's bucket level in bits (signed); set: write it instead"""
+        v = ctypes.c_int64(0 if set is None else int(set))
+        self._chk(lib.scroll_batch_dyn_rate_level(self.h, s, ctypes.byref(v), 0 if set is None else 1),
+                  "dyn_rate_level")
+        return v.value
 
     def last_bytes(self):
         return lib.scroll_batch_last_bytes(self.h)

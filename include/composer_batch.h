@@ -201,7 +201,8 @@ int scroll_batch_set_dyn_refs(ScrollBatch *b, int s, const uint8_t *ref_a, const
  *   scroll_batch_set_dyn_qp_at(b, s, f, qp)    under UI hints (the rect in the
  *       frame's hint record): frame f of stream s at QP qp, -1 = the
  *       stream's.  There the slice QP stays 26 and the rect's first MB with a
- *       residual carries mb_qp_delta qp - 26, the others 0.
+ *       residual carries mb_qp_delta qp - 26, the others 0.  (Without hints a
+ *       frame's own QP is scroll_batch_set_dyn_qp_frames', further down.)
  *   A stream with the deblocking filter on (no
  *   deblocking_filter_control_present_flag, e.g. an ingested one) keeps QP 26:
  *   another QP would change the filtering of its scroll MBs (SCROLL_ERR_CONFIG). */
@@ -404,6 +405,108 @@ float scroll_batch_dyn_probe_ms(ScrollBatch *b);   /* with enable_timing; -1 wit
  * reference it lacks while the fallback is off (the compose would fail the
  * stream); SCROLL_ERR_DEVICE as above. */
 int scroll_batch_dyn_probe_hinted(ScrollBatch *b, int nframes, const uint8_t *qps, int nq, void *hip_stream);
+
+/* ---- the plain rect at a QP of its own per frame ----
+ * A table of one byte per (stream, frame of the compose) on the device,
+ * [s * stream_stride + f]: 0xFF the stream's QP (scroll_batch_set_dyn_qp /
+ * _stream), any other value that frame's QP, 0..51 (a byte above 51 that a
+ * caller's own kernel writes counts as 0xFF).  Entry f applies to frame f of
+ * every following scroll_batch_compose of the plain dynamic rect until it is
+ * changed or cleared, whatever nframes that compose has.  Frame f's dynamic
+ * scroll NAL then carries slice_qp_delta = its QP - 26 and is coded, decoded
+ * (scroll_batch_set_dyn_recon) and measured at that QP; a frame below 22 goes
+ * the general path on its own, beside int8 frames of the same stream.  An
+ * entry of a frame without a dynamic NAL (a waypoint frame in experiment
+ * mode) is ignored.  Prediction is from the static pictures only, so frame
+ * f's NAL is the NAL of a compose with every frame at that QP.  Bit-exact
+ * definition: oracle/dyn_oracle.h or_compose_dyn, called per frame with the
+ * frame's QP in its or_dyn_rect.
+ * The table is allocated by the first call below that needs it and freed by
+ * scroll_batch_set_dyn_rect and scroll_batch_destroy; without it no compose
+ * gains a launch, an allocation or a changed byte.
+ *
+ *   scroll_batch_set_dyn_qp_frames(b, s, f0, n, qps)   entries f0 .. f0 + n - 1
+ *       of stream s (s = -1: of every stream) from qps[0..n), -1 = the
+ *       stream's QP.  SCROLL_ERR_CONFIG without the dynamic rect or with UI
+ *       hints set (under hints the per-frame QP is scroll_batch_set_dyn_qp_at's),
+ *       and for a QP other than 26 or -1 on a stream with the deblocking
+ *       filter on; SCROLL_ERR_ARG for a range outside 0..max_frames or a QP
+ *       outside -1..51.  Synchronises the batch.  Frames below 22 get their
+ *       general-path record slots here, not at a failing compose.
+ *   scroll_batch_clear_dyn_qp_frames(b)   every entry back to 0xFF.
+ *   scroll_batch_dyn_qp_frames(b, s, f0, n, out)   the entries as they stand on
+ *       the device (-1 for 0xFF), after everything queued on the batch's last
+ *       stream and the last pick's: how a caller learns what
+ *       scroll_batch_dyn_pick chose.  All -1 before the table exists.
+ *   scroll_batch_dyn_qp_frames_device(b, &stream_stride)   the table itself, for
+ *       a caller's own kernel on the compose's stream (allocated, all 0xFF,
+ *       if it was not; NULL without the dynamic rect or when that fails).
+ *       The general-path pool is then sized for whatever QPs it may hold by
+ *       the existing overflow status: a compose that runs out fails the
+ *       frames concerned with SCROLL_ERR_OVERFLOW, grows the pool, and the
+ *       caller composes again.
+ * A scroll_batch_compose with UI hints set while any entry differs from 0xFF
+ * returns SCROLL_ERR_CONFIG and commits nothing. */
+int scroll_batch_set_dyn_qp_frames(ScrollBatch *b, int s, int f0, int n, const int8_t *qps);
+int scroll_batch_clear_dyn_qp_frames(ScrollBatch *b);
+int scroll_batch_dyn_qp_frames(ScrollBatch *b, int s, int f0, int n, int8_t *out);
+uint8_t *scroll_batch_dyn_qp_frames_device(ScrollBatch *b, size_t *stream_stride);
+
+/* ---- picking those QPs on the device, from the probe ----
+ * scroll_batch_dyn_pick(b, nframes, &rate, frame_bits_per_stream, hip_stream)
+ * reads the last scroll_batch_dyn_probe's device results and row counters and
+ * writes entries 0 .. nframes - 1 of every stream of the table above: no
+ * result crosses to the host.  Asynchronous on hip_stream (0 = the batch's
+ * own), which must be the stream of the probe before it and of the compose
+ * after it.
+ *
+ * The cost of candidate k of a frame is the QP-dependent part of its NAL's
+ * RBSP bits, cost(k) = bits[k] + len(se(qp[k] - 26)) (C(frame) above cancels).
+ * pick(allow): among the candidates with cost <= allow the smallest
+ * sse[0] + sse[1] + sse[2]; ties go to the smaller cost, then to the earlier
+ * candidate.  If none fits, the candidate with the smallest cost (ties to the
+ * smaller error, then to the earlier one), reported as over.
+ *   SCROLL_DYN_RATE_FRAME    allow = frame_bits for every frame; stateless.
+ *   SCROLL_DYN_RATE_BUCKET   a leaky bucket per stream, its signed 64-bit level
+ *       kept on the device across calls.  Every frame of the pick in order --
+ *       a frame that gets no choice included, at cost 0 --
+ *           allow = min(bucket_bits, level + frame_bits)
+ *           pick(max(allow, 0))
+ *           level = max(allow - cost(chosen), -bucket_bits).
+ *       The level moves at the pick, not at the compose: a pick that is not
+ *       followed by its compose, or is made twice, has still spent.
+ *       scroll_batch_set_dyn_rect resets every level to 0.
+ * frame_bits_per_stream: num_streams host values replacing rate.frame_bits,
+ * or NULL.
+ * A frame gets its chosen QP; it gets 0xFF and no choice when the probe found
+ * no dynamic NAL in it, when its stream has the deblocking filter on (it
+ * keeps QP 26), or when the probe did not count every rect row of it.
+ * With a candidate below 22 the general-path record pool is sized here for
+ * every frame taking one (this call then synchronises the batch once).
+ * SCROLL_ERR_CONFIG before any plain probe, when the last probe was the
+ * hinted one, for nframes beyond the last probe's, and with UI hints set;
+ * SCROLL_ERR_ARG for a NULL rate or an unknown mode.
+ *
+ *   scroll_batch_dyn_pick_result(b, s, f, &k, &qp)   frame f of stream s of the
+ *       last pick; synchronises its stream.  0: candidate k at QP qp within
+ *       the allowance; 1: the cheapest candidate, over it; 2: nothing chosen,
+ *       the frame keeps the stream's QP (k and qp are -1); SCROLL_ERR_DEVICE
+ *       for a frame whose rows were not all counted; SCROLL_ERR_CONFIG before
+ *       any pick; SCROLL_ERR_ARG outside the last pick.
+ *   scroll_batch_dyn_rate_level(b, s, &level, set)   stream s's bucket level:
+ *       set = 0 reads it (after the last pick), set != 0 writes *level. */
+#define SCROLL_DYN_RATE_FRAME  0
+#define SCROLL_DYN_RATE_BUCKET 1
+typedef struct {
+    uint32_t mode;          /* SCROLL_DYN_RATE_* */
+    uint32_t frame_bits;    /* FRAME: the allowance; BUCKET: what every frame adds to the level */
+    uint32_t bucket_bits;   /* BUCKET: the level's cap, and the cap of its debt */
+    uint32_t pad;
+} ScrollDynRate;
+int scroll_batch_dyn_pick(ScrollBatch *b, int nframes, const ScrollDynRate *rate,
+                          const uint32_t *frame_bits_per_stream, void *hip_stream);
+int scroll_batch_dyn_pick_result(ScrollBatch *b, int s, int f, int *k, int *qp);
+int scroll_batch_dyn_rate_level(ScrollBatch *b, int s, int64_t *level, int set);
 /* HIP-event ms of the timed composes since the last call: plan (both
  * passes), emit, dyn stage (= dyn code + dyn pack), dyn emit, dyn code
  * (k_dyn_rows + k_dyn_code), dyn pack (k_dyn_group + k_dyn_ep); accumulators reset
