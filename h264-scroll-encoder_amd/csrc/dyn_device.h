@@ -1123,9 +1123,11 @@ __device__ __host__ inline uint32_t tzrb_entry(const Tabs &T, uint32_t nz, int m
  * the first level after fewer than three trailing ones (levelCode - 2), x
  * level v in [-LVT_V, LVT_V] at index v + LVT_V + 1.  Entry = codeword value
  * (the bits after level_prefix's zeros: at most 13) | its length << 13 | the
- * next level's class (suffixLength after this level) << 18.  Levels past
- * LVT_V take the arithmetic form. */
-constexpr int LVT_V = 47, LVT_W = 96, LVT_C = 9, LVT_N = LVT_C * LVT_W;
+ * next level's class (suffixLength after this level) as the byte offset of
+ * its row of the table (4 LVT_W a class, at most 6 of them: 12 bits) << 18,
+ * so the next entry's address is one shift-add.  Levels past LVT_V take the
+ * arithmetic form. */
+constexpr int LVT_V = 47, LVT_W = 96, LVT_C = 9, LVT_N = LVT_C * LVT_W, LVT_ROW = 4 * LVT_W;
 __device__ __host__ constexpr uint32_t lvt_entry(int c, int v)
 {
     if (v == 0 || v > LVT_V || v < -LVT_V) return 0u;
@@ -1145,7 +1147,7 @@ __device__ __host__ constexpr uint32_t lvt_entry(int c, int v)
     }
     const int s1 = sl == 0 ? 1 : sl;
     const int nx = s1 + ((a > (3 << (s1 - 1)) && s1 < 6) ? 1 : 0);
-    return fv | fl << 13 | (uint32_t)nx << 18;
+    return fv | fl << 13 | (uint32_t)(nx * LVT_ROW) << 18;
 }
 struct LvTab {
     uint32_t e[LVT_N];
@@ -1192,23 +1194,30 @@ __device__ __host__ inline int cavlc_body_t(CAP &cap, const int8_t *lb, uint32_t
     const uint32_t s3 = ((uint32_t)v0 >> 31) << 2 | ((uint32_t)v1 >> 31) << 1 | ((uint32_t)v2 >> 31);
     uint64_t acc = s3 >> (3 - t1);                         /* the trailing-one signs, first one first */
     uint32_t an = (uint32_t)t1;
-    uint32_t m = (t1 == 0 ? g0 : (t1 == 1 ? g1 : (t1 == 2 ? g2 : g3))) >> 1;
+    uint32_t g = t1 == 0 ? g0 : (t1 == 1 ? g1 : (t1 == 2 ? g2 : g3));      /* the levels left, over the guard bit */
+    uint32_t m = g >> 1;
     auto push = [](uint64_t &ac, uint32_t &n, uint32_t v, uint32_t len, CAP &c) {
-        if (n + len > 64u) {                               /* rare: spill */
+        uint32_t n2 = n + len;                             /* one sum for the test and the count */
+        if (n2 > 64u) {                                    /* rare: spill */
             if (n > 32u) c.put((uint32_t)(ac >> 32), (int)(n - 32u));
             c.put((uint32_t)ac, n > 32u ? 32 : (int)n);
             ac = 0;
-            n = 0;
+            n2 = len;
         }
         ac = (ac << len) | v;
-        n += len;
+        n = n2;
     };
     /* the level class (lvt_entry): suffixLength, +7 for the first level
-     * after fewer than three trailing ones */
-    int cls = ((tc > 10 && t1 < 3) ? 1 : 0) + (t1 < 3 ? 7 : 0);
+     * after fewer than three trailing ones -- kept as the byte offset of
+     * the class's row of the table, as the entries give the next one */
+    uint32_t cls = (uint32_t)((((tc > 10 && t1 < 3) ? 1 : 0) + (t1 < 3 ? 7 : 0)) * LVT_ROW);
+    auto entry = [lvt](uint32_t row, int v) -> uint32_t {      /* |v| <= LVT_V */
+        return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(lvt + LVT_V + 1) + ((int)row + 4 * v));
+    };
     /* the level codeword from the table, or (|v| > LVT_V) the arithmetic form */
-    auto level_code = [&](int v, int cl) -> uint32_t {
-        if (v >= -LVT_V && v <= LVT_V) return lvt[cl * LVT_W + v + LVT_V + 1];
+    auto level_code = [&](int v, uint32_t row) -> uint32_t {
+        if (v >= -LVT_V && v <= LVT_V) return entry(row, v);
+        const int cl = (int)row / LVT_ROW;
         const int sl = cl >= 7 ? cl - 7 : cl, adj = cl >= 7 ? 2 : 0;
         const int a = v < 0 ? -v : v;
         const int code = 2 * a - 2 + (v < 0 ? 1 : 0) - adj;
@@ -1220,32 +1229,38 @@ __device__ __host__ inline int cavlc_body_t(CAP &cap, const int8_t *lb, uint32_t
         fv = e15 ? (uint32_t)(4096 + code - lim) : (e14 ? (uint32_t)(code + 2) : fv);
         fl = e15 ? 28u : (e14 ? 19u : fl);
         const int s1 = sl == 0 ? 1 : sl;
-        return fv | fl << 13 | (uint32_t)(s1 + ((a > (3 << (s1 - 1)) && s1 < 6) ? 1 : 0)) << 18;
+        return fv | fl << 13 | (uint32_t)((s1 + ((a > (3 << (s1 - 1)) && s1 < 6) ? 1 : 0)) * LVT_ROW) << 18;
     };
     /* round 6: the loop holds the table path only (levels clamped into the
      * table, a lane whose block has a level past LVT_V flagged), so the rare
      * arithmetic form costs no exec-mask branch per level; a flagged lane
      * codes its block again below with it.  The next level's byte is read
      * one iteration ahead, so each level waits for one LDS round trip (its
-     * codeword) instead of two; past the last level m is 0 and the read is
-     * the guard byte lb[-1] (unused) */
+     * codeword) instead of two; past the last level only the guard bit is
+     * left and the read is the guard byte lb[-1] (unused; k_dyn_row's block
+     * 0 has the byte before its records there, inside the workgroup's LDS).
+     * The levels left are found over the guard bit (g is never 0: one count
+     * of leading zeros gives the byte, no zero test), the loop ends when
+     * only the guard is left (no count kept beside the mask), and the flag
+     * gathers in a register (the difference the clamp made, tested once
+     * after the loop) instead of a compare and a lane-mask OR per level */
     const uint32_t m0 = m, an0 = an;
     const uint64_t acc0 = acc;
-    const int cls0 = cls;
+    const uint32_t cls0 = cls;
     const CAP cap0 = cap;
-    bool big = false;
-    int pn = top_bit(m);
-    int vn = (int)lb[pn];
-    for (int k = t1; k < tc; ++k) {                        /* levels below the trailing ones */
+    uint32_t big = 0;
+    int cn = __builtin_clz(g);
+    int vn = (int)lb[30 - cn];
+    while (g > 1u) {                                       /* levels below the trailing ones: bits over the guard */
         const int v = vn;
-        m &= ~(1u << pn);
-        pn = top_bit(m);
-        vn = (int)lb[pn];
+        g &= ~(0x80000000u >> cn);                         /* the level's bit (cn < 31 here) */
+        cn = __builtin_clz(g);
+        vn = (int)lb[30 - cn];
         const int vc = v < -LVT_V ? -LVT_V : (v > LVT_V ? LVT_V : v);
-        big |= vc != v;
-        const uint32_t e = lvt[cls * LVT_W + vc + LVT_V + 1];
+        big |= (uint32_t)(vc ^ v);
+        const uint32_t e = entry(cls, vc);
         push(acc, an, e & 0x1fffu, (e >> 13) & 31u, cap);
-        cls = (int)(e >> 18);
+        cls = e >> 18;
     }
     if (big) {                                             /* rare: the block again, exact */
         m = m0;
@@ -1258,7 +1273,7 @@ __device__ __host__ inline int cavlc_body_t(CAP &cap, const int8_t *lb, uint32_t
             m &= ~(1u << p);
             const uint32_t e = level_code((int)lb[p], cls);
             push(acc, an, e & 0x1fffu, (e >> 13) & 31u, cap);
-            cls = (int)(e >> 18);
+            cls = e >> 18;
         }
     }
     /* total_zeros + run_before: the entry's code, len = 31 - ctz */

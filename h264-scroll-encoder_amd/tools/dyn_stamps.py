@@ -55,8 +55,9 @@ def main():
     b.compose(F, rewind=True)
     assert b.sync() == 0, hs.last_error()
     mbh = H // 16
-    na = max(1, -(-rect[1] // 64))                 # DYN_STATIC_ROWS = 64
-    ng = na + rect[3] + max(1, -(-(mbh - rect[1] - rect[3]) // 64))
+    sr = 16                                        # DYN_STATIC_ROWS (engine.h)
+    na = max(1, -(-rect[1] // sr))
+    ng = na + rect[3] + max(1, -(-(mbh - rect[1] - rect[3]) // sr))
     nslot = (2 + ng) * S * F
     buf = (ctypes.c_uint64 * (nslot * 8))()
     got = hs.lib.scroll_batch_debug_stamps(b.h, buf, nslot)

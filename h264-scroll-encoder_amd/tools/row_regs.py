@@ -2,6 +2,7 @@
 """row_regs.py -- register budget and spill traffic of k_dyn_row, without a GPU.
 
     python h264-scroll-encoder_amd/tools/row_regs.py [-D...] [--src FILE] [--keep OUT.s | --listing IN.s]
+                                                     [--inst TEXT] [--phase N]
 
 Compiles csrc/dyn_kernels.hip device-only to gfx950 assembly with the
 Makefile's flags (plus any -D given) and prints, for every k_dyn_row
@@ -9,13 +10,18 @@ instantiation:
   * the code object's metadata (SGPRs, VGPRs, spills, private segment, LDS);
   * per barrier-delimited phase (phase n = the code between the n-th and the
     n+1-th s_barrier in program order) the number of VALU and SALU
-    instructions and of the lane operations (v_readlane_b32 / v_writelane_b32)
-    an SGPR spilled to a VGPR lane turns into;
+    instructions, of the lane operations (v_readlane_b32 / v_writelane_b32)
+    an SGPR spilled to a VGPR lane turns into, of the branch / wait / control
+    instructions (ctl) and of the memory instructions (mem: LDS, buffer,
+    global, scalar loads);
   * per loop (a backward branch to a label) the same counts with the source
     lines of dyn_kernels.hip the loop's instructions come from, so a loop
     that reloads or saves a spilled value is named.
 The counts are static: one per instruction in the listing, whatever its trip
-count.
+count.  --inst keeps the instantiations whose name holds TEXT (e.g. "<false,
+false>"); --phase N lists only the loops inside phase N (3 is the CAVLC
+stretch of the normal path: sort scatter's barrier to the records' one), so
+two revisions' level loops can be set side by side.
 """
 import argparse
 import collections
@@ -94,24 +100,27 @@ def count(ins):
 
 
 def fmt(c):
-    return "VALU %5d  SALU %5d  lane ops %4d" % (c["valu"], c["salu"], c["lane"])
+    return "VALU %5d  SALU %5d  lane ops %4d  ctl %4d  mem %4d" % (c["valu"], c["salu"], c["lane"], c["sctl"],
+                                                                   c["mem"] + c["smem"])
 
 
-def report(name, lines, meta, files):
+def report(name, lines, meta, files, only_phase=None):
     ins, labels = parse_body(lines, files)
     print("== " + name)
     for k in META:
         if k in meta:
             print("   %-30s %s" % (k, meta[k]))
     print("   body: %d instructions, %s" % (len(ins), fmt(count(ins))))
-    ph, cur = [], []
-    for i in ins:
+    ph, cur, bounds, start = [], [], [], 0
+    for n, i in enumerate(ins):
         if i[0] == "s_barrier":
             ph.append(cur)
-            cur = []
+            bounds.append((start, n))
+            cur, start = [], n + 1
         else:
             cur.append(i)
     ph.append(cur)
+    bounds.append((start, len(ins)))
     print("   phases (between s_barrier instructions, program order):")
     for n, p in enumerate(ph):
         src = sorted({l for _, _, l in p if l})
@@ -123,6 +132,9 @@ def report(name, lines, meta, files):
             loops[labels[ops.strip()]] = i
     print("   loops (a label with backward branches to it; nested loops count in their parents too):")
     for a, b in sorted(loops.items()):
+        if only_phase is not None and not (only_phase < len(bounds) and bounds[only_phase][0] <= a and
+                                           b < bounds[only_phase][1]):
+            continue
         body = ins[a:b + 1]
         src = collections.Counter(l for _, _, l in body if l)
         top = sorted(l for l, _ in src.most_common(3))
@@ -138,6 +150,8 @@ def main():
     ap.add_argument("--keep", help="keep the assembly listing here")
     ap.add_argument("--listing", help="read this listing instead of compiling")
     ap.add_argument("--kernel", default="k_dyn_row", help="kernels whose name holds this (default k_dyn_row)")
+    ap.add_argument("--inst", help="only the instantiations whose demangled name holds this")
+    ap.add_argument("--phase", type=int, help="list only the loops inside this phase")
     args, defs = ap.parse_known_args()
     with tempfile.TemporaryDirectory() as td:
         out = args.listing or args.keep or os.path.join(td, "dyn_kernels.s")
@@ -160,11 +174,12 @@ def main():
     files = {m.group(1) for m in (re.match(r'\s*\.file\s+(\d+)\s.*"([^"]*)"(?:\s+md5.*)?$', ln) for ln in text)
              if m and os.path.basename(m.group(2)) == base}
     names = demangle([k for k in metas if args.kernel in k])
-    syms = [k for k in names if re.search(r"\b" + re.escape(args.kernel) + r"\b", names[k])]
+    syms = [k for k in names if re.search(r"\b" + re.escape(args.kernel) + r"\b", names[k])
+            and (not args.inst or args.inst in names[k])]
     for sym in sorted(syms, key=lambda k: names[k]):
         a = next(i for i, ln in enumerate(text) if ln.startswith(sym + ":"))
         b = next(i for i in range(a, len(text)) if text[i].strip().startswith(".Lfunc_end"))
-        report(re.sub(r"^void |\(anonymous namespace\)::|\(.*$", "", names[sym]), text[a + 1:b], metas[sym], files)
+        report(re.sub(r"^void |\(anonymous namespace\)::|\(.*$", "", names[sym]), text[a + 1:b], metas[sym], files, args.phase)
     if not syms:
         sys.exit("no kernel named *%s* in the listing" % args.kernel)
 
