@@ -50,10 +50,6 @@ __constant__ PTabs g_ptabs = make_ptabs(k_tabs);
  * table: 384 KB, filled once per device by k_tzrb_init; mostly L2-resident
  * (the masks of real blocks are few) */
 __device__ uint32_t g_tzrb[TZRB_N];
-/* level codewords (lvt_entry), copied into k_dyn_row's bit window for its
- * CAVLC phase */
-__constant__ LvTab g_lvt = make_lvt();
-
 /* the quantiser at every rect QP, luma and chroma (QPc, Table 8-15): one
  * uniform index -> scalar loads (qparams_rt's six-way selects compiled to a
  * branch maze per workgroup) */
@@ -84,24 +80,6 @@ __device__ inline void load_ptabs(PTabs &dst, int t, int nthr)
     static_assert(sizeof(PTabs) % 16 == 0, "PTabs copies as uint4");
     for (int i = t; i < N; i += nthr) reinterpret_cast<uint4 *>(&dst)[i] = reinterpret_cast<const uint4 *>(&g_ptabs)[i];
 }
-
-/* RowTabs from g_ptabs, one 32-bit word per thread and step */
-__device__ inline void load_rowtabs(RowTabs &dst, int t, int nthr)
-{
-    constexpr int NC = (int)(sizeof(dst.ct) / 4), NZ = (int)(sizeof(dst.tzdc) / 4), NR = (int)(sizeof(dst.rb) / 4);
-    static_assert(sizeof(dst.ct) % 4 == 0 && sizeof(dst.tzdc) % 4 == 0 && sizeof(dst.rb) % 4 == 0, "word copies");
-    const uint32_t *ct = reinterpret_cast<const uint32_t *>(g_ptabs.ct);
-    const uint32_t *tz = reinterpret_cast<const uint32_t *>(g_ptabs.tzdc);
-    const uint32_t *rb = reinterpret_cast<const uint32_t *>(g_ptabs.rb);
-    uint32_t *dc = reinterpret_cast<uint32_t *>(dst.ct), *dz = reinterpret_cast<uint32_t *>(dst.tzdc);
-    uint32_t *dr = reinterpret_cast<uint32_t *>(dst.rb);
-    for (int i = t; i < NC + NZ + NR; i += nthr) {
-        if (i < NC) dc[i] = ct[i];
-        else if (i < NC + NZ) dz[i - NC] = tz[i - NC];
-        else dr[i - NC - NZ] = rb[i - NC - NZ];
-    }
-}
-
 
 constexpr int HEAD_MAX = 160;           /* bits of one MB head (huge mvd: 2 x 63 + ref) */
 constexpr int HDR_MAX = 1024;           /* slice header bits (8 waypoints + MMCO ~ 250) */
@@ -1276,8 +1254,11 @@ constexpr int ROW_NPMAX = 8;                    /* tasks per thread at most (153
 #endif
 constexpr int ROW_GB = SCROLL_ROW_GB;           /* bit window: 28 Kbit (a config-3 row ~18 Kbit, one pass) */
 
+constexpr int ROW_PCD_N = (NPC + 3) & ~3;      /* pcd in whole 16-byte vectors */
+
 struct RowFixed {
     RowTabs ptabs;
+    uint32_t pcd[ROW_PCD_N];                     /* per piece class: its nC neighbours (pc_desc) */
     union {                                      /* the sort's counts and the level table are dead before the bit window */
         uint32_t buf[ROW_GB + 4];                /* + ROW_PAD: put_piece1's spare words */
         struct {
@@ -1293,12 +1274,11 @@ struct RowFixed {
     uint32_t rt[32];                             /* the row's prediction-row table (k_dyn_rows) */
     uint32_t ncand;                              /* EP candidate words of the row */
     uint32_t spill;                              /* its spill slot (a row over its slot) */
-    uint32_t pcd[NPC];                           /* per piece class: its nC neighbours (pc_desc) */
 };
 
 static_assert(2 * SORT_KEYS <= 32 && 32 + LVT_N <= ROW_GB, "the sort counts and the level table share the bit window");
 static_assert(ROW_PAD == 4, "RowFixed::buf holds ROW_PAD spare words");
-static_assert(offsetof(RowFixed, lvt) % 8 == 0, "the level table is copied in 8-byte words");
+static_assert(sizeof(RowFixed) <= 4992, "eight config-3 row workgroups per CU");
 
 /* dynamic LDS of k_dyn_row: lv [NPC w] uint4 (levels, then bodies), moff
  * [w + 1] u32 (the rect columns' bit offsets in the row; the static
@@ -1360,6 +1340,41 @@ __host__ __device__ constexpr uint32_t pc_desc(int pc)
     return (uint32_t)(da + 32) | (al ? 1u : 0u) << 6 | (uint32_t)(db + 32) << 7 | (bt ? 1u : 0u) << 13 |
            (uint32_t)e << 14;
 }
+
+/* k_dyn_row's constant tables -- coeff_token and the chroma DC fields of
+ * g_ptabs, pc_desc of every piece class, the level codewords (lvt_entry) --
+ * packed as they lie in its LDS (RowFixed: ptabs, pcd, then lvt past the
+ * sort's 32 words), so one wave copies them 16 bytes a lane, no branch */
+struct alignas(16) RowConst {
+    RowTabs ptabs;
+    uint32_t pcd[ROW_PCD_N];
+    uint32_t lvt[LVT_N];
+};
+constexpr RowConst make_rowconst(const Tabs &T)
+{
+    RowConst C{};
+    const PTabs P = make_ptabs(T);
+    for (int i = 0; i < 4 * 68; ++i) C.ptabs.ct[i / 68][i % 68] = P.ct[i / 68][i % 68];
+    for (int i = 0; i < 12; ++i) C.ptabs.tzdc[i / 4][i % 4] = P.tzdc[i / 4][i % 4];
+    for (int i = 0; i < 7 * 16; ++i) C.ptabs.rb[i / 16][i % 16] = P.rb[i / 16][i % 16];
+    for (int i = 0; i < NPC; ++i) C.pcd[i] = pc_desc(i);
+    const LvTab V = make_lvt();
+    for (int i = 0; i < LVT_N; ++i) C.lvt[i] = V.e[i];
+    return C;
+}
+__constant__ RowConst g_rowconst = make_rowconst(k_tabs);
+/* in 16-byte vectors: the table, its part in front of the sort's words, the
+ * sort's words skipped in LDS */
+constexpr int ROWC_NV = (int)(sizeof(RowConst) / 16), ROWC_HEAD = (int)(offsetof(RowConst, lvt) / 16);
+constexpr int ROWC_GAP = (int)((offsetof(RowFixed, lvt) - offsetof(RowConst, lvt)) / 16);
+static_assert(offsetof(RowFixed, ptabs) == 0 && offsetof(RowFixed, pcd) == offsetof(RowConst, pcd) &&
+                  offsetof(RowFixed, kc) == offsetof(RowConst, lvt) && offsetof(RowFixed, lvt) % 16 == 0 &&
+                  sizeof(RowConst) % 16 == 0 && sizeof(RowConst) == 16 * ROWC_HEAD + 4 * LVT_N,
+              "RowConst is RowFixed's head without the sort's words");
+static_assert(offsetof(RowFixed, wl) == offsetof(RowFixed, wo) + 32 && offsetof(RowFixed, wv) == offsetof(RowFixed, wo) + 64 &&
+                  offsetof(PlanPending, wl) == offsetof(PlanPending, wo) + 32 &&
+                  offsetof(PlanPending, wv) == offsetof(PlanPending, wo) + 64,
+              "the waypoint table copies as 24 words");
 
 /* LDS of ep_fix: the row-group table, candidate bases, the position
  * bitmap / list (ep_fix's LCAP words) and four counters */
@@ -1543,6 +1558,44 @@ __device__ inline T karg_at(KargPtr p, size_t off)
 /* field F of the kernel's RowArgs through K = kargs_here() */
 #define row_arg(K, F) karg_at<decltype(RowArgs::F)>(K, offsetof(RowArgs, F))
 
+/* Everything k_dyn_row reads first after its levels, copied into LDS by one
+ * wave (lane = its lane): the constant tables (g_rowconst), the stream's
+ * waypoint table (pend) and the NAL's 12 MB-head classes with their lengths
+ * (k_dyn_rows).  Every load is issued before the first LDS write -- one
+ * round trip -- and nothing branches: a lane past a table's end takes its
+ * last element again and writes the same value to the same word.  The
+ * sort's words between pcd and lvt are not written (they are counting while
+ * the normal path runs this).  head_over is this wave's alone to write. */
+__device__ inline void row_copy_tabs(RowFixed &L, int s, size_t nb, int lane)
+{
+    constexpr int NK = (ROWC_NV + 63) / 64;
+    const KargPtr K = kargs_here();
+    const int32_t *pw = reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(row_arg(K, pend) + s) +
+                                                          offsetof(PlanPending, wo));
+    const uint4 *hv = row_arg(K, heads) + nb * DYN_HEAD_VECS;
+    const uint4 *src = reinterpret_cast<const uint4 *>(&g_rowconst);
+    const int l24 = min(lane, 23), l12 = min(lane, 11);
+    uint4 v[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) v[k] = src[min(lane + 64 * k, ROWC_NV - 1)];
+    const int32_t wp = pw[l24];
+    const uint4 m = hv[l12];
+    const uint32_t hl = reinterpret_cast<const uint32_t *>(hv + 12)[l12];
+    uint4 *dst = reinterpret_cast<uint4 *>(&L);
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int i = min(lane + 64 * k, ROWC_NV - 1);
+        dst[i + (i >= ROWC_HEAD ? ROWC_GAP : 0)] = v[k];
+    }
+    /* wo, wl, wv: 24 adjacent words */
+    reinterpret_cast<int32_t *>(reinterpret_cast<char *>(&L) + offsetof(RowFixed, wo))[l24] = wp;
+    L.hhi[l12] = (uint64_t)m.x << 32 | m.y;
+    L.hlo[l12] = (uint64_t)m.z << 32 | m.w;
+    L.hlen[l12] = hl & 0x7fffffffu;
+    const bool over = __builtin_amdgcn_ballot_w64(lane < 12 && (hl >> 31)) != 0;
+    if (lane == 0) L.head_over = over;
+}
+
 /* grid (h, frames, streams), row_threads(w) threads, row_lds_bytes dynamic LDS.
  * GEN: the instantiation for the NALs k_dyn_rows flagged for the general
  * path (records from k_dyn_code_general); the other one codes the rest --
@@ -1575,10 +1628,11 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     const size_t nb = (size_t)s * ld_fr + f;
     constexpr bool general = GEN;
     constexpr int SR = DYN_STATIC_ROWS;
+    /* the workgroup's slot, a uniform pointer (thread 0 writes: as thread
+     * 0's own value it was a VGPR pair held to the kernel's end) */
     uint64_t *stp = nullptr;
-    if (DBG && stamps && t == 0)
-        stp = stamps + (((size_t)s * gridDim.y + f) * g.ngroups + (max(1, (g.y0 + SR - 1) / SR) + r)) * 8;
-    if (stp) stp[0] = t_entry;
+    if (DBG && stamps) stp = stamps + (((size_t)s * gridDim.y + f) * g.ngroups + (max(1, (g.y0 + SR - 1) / SR) + r)) * 8;
+    if (stp && t == 0) stp[0] = t_entry;
     const Rect R{g.x0, g.y0, g.w, g.h};
     const int w = R.w, ndt = R.w * R.h, row = R.y0 + r, npc = NPC * w, ntask = 24 * w;
     const int nA = max(1, (R.y0 + SR - 1) / SR);
@@ -1601,6 +1655,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
      * LDS copy of the table (a frame this instantiation does not code reads
      * a table k_dyn_rows did not write: offsets into the descriptors' ranges
      * or past them, which read 0; nothing is stored) */
+    const DynFrame df = a.dfr[nb];      /* a scalar load, on its way while the offsets' vector loads are */
     FetchOff fo;
     fo.pb = -1;
     bool fo_chroma = false;
@@ -1608,10 +1663,24 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     if (!general) {
         const uint32_t *rtg = rows + nb * (size_t)(32 * g.h);
         const int k0 = kind_of(0);
+        /* the row's entry t % 32 of that table, for its LDS copy (rt): issued
+         * with the offsets' loads, one round trip for both */
+        const int e = t & 31;
+        const uint32_t rtv = rtg[e < 16 ? 16 * r + e : 16 * g.h + (e < 24 ? 8 * r + e - 16 : 8 * g.h + 8 * r + e - 24)];
         if (k0 == 0) {
             fetch_luma(fo, t, r, g, rtg + 16 * r);
             fo.pb = 0;
             fetch_pass9(fo, 0u, (uint32_t)(16 * w), fs, rb, nx);
+            /* luma never reads c: left as the compiler's copy of b[3] (the
+             * ninth load folds into the eighth) it made the wave wait here
+             * for its four prediction rows */
+            nx.c = 0u;
+            /* wave 0 is a luma wave at every width.  Behind the pixel loads
+             * in program order, so the wait leaves those nine in flight;
+             * every lane of every luma wave stores (the same 32 words): a
+             * store under t < 32 took the load into its exec-mask region,
+             * behind a full wait */
+            L.rt[e] = rtv;
         } else if (k0 == 1) {
             fetch_chroma(fo, t - L0, r, g, csz, rtg + 16 * g.h + 8 * r, rtg + 24 * g.h + 8 * r);
             fo.pb = 0;
@@ -1619,7 +1688,6 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             fetch_pass9(fo, 0u, (uint32_t)(8 * w), fs, rb, nx);
         }
     }
-    const DynFrame df = a.dfr[nb];
     if (df.nal < 0 || ((df.err & DF_GENERAL) != 0) != GEN) return;
 
     uint4 *lv = rdyn;
@@ -1629,36 +1697,34 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     uint8_t *ta = reinterpret_cast<uint8_t *>(off16 + npc), *cbpa = ta + 8 * w, *codea = cbpa + w;
     uint32_t *mbits = reinterpret_cast<uint32_t *>(ta);   /* phase 4 on: ta is dead after phase 3 */
 
-    if (t < 8) {
-        L.wo[t] = a.pend[s].wo[t];
-        L.wl[t] = a.pend[s].wl[t];
-        L.wv[t] = a.pend[s].wv[t];
-    }
-    if (t == 0) {
-        L.head_over = 0;
-        L.ncand = 0;
-    }
-    if (t < 12) {                       /* the NAL's MB-head classes (k_dyn_rows) */
-        const uint4 *hv = a.heads + nb * DYN_HEAD_VECS;
-        const uint4 m = hv[t];
-        const uint32_t hl = reinterpret_cast<const uint32_t *>(hv + 12)[t];
-        L.hhi[t] = (uint64_t)m.x << 32 | m.y;
-        L.hlo[t] = (uint64_t)m.z << 32 | m.w;
-        L.hlen[t] = hl & 0x7fffffffu;
-        if (hl >> 31) L.head_over = 1;                  /* after lane 0's 0 (same wave, same word) */
-    }
+    /* Before the first barrier only what the levels need: the row table,
+     * the sort's zeroed counts, the quantiser.  Everything first read after
+     * the levels (the constant tables, the waypoint table, the head classes)
+     * is row_copy_tabs', run by the last wave once its own level passes are
+     * done (it never has more of them than the others); the general path has
+     * no levels and copies here. */
+    if (t == 0) L.ncand = 0;
     if (t < SORT_KEYS) L.kc[0][t] = 0u;
-    if (t < NPC) L.pcd[t] = pc_desc(t);
-    load_rowtabs(L.ptabs, t, T);
-    for (int i = t; i < LVT_N / 2; i += T)      /* 8-byte aligned in LDS */
-        reinterpret_cast<uint2 *>(L.lvt)[i] = reinterpret_cast<const uint2 *>(&g_lvt)[i];
-    if (!general && t < 32) L.rt[t] = rows[nb * (size_t)(32 * g.h) + (t < 16 ? 16 * r + t : 16 * g.h + (t < 24 ? 8 * r + t - 16 : 8 * g.h + 8 * r + t - 24))];
+    if (general && wv0 == T - 64) row_copy_tabs(L, s, nb, lane);
+    /* the quantiser at the frame's rect QP (k_dyn_rows; QP_MIN and up on
+     * the normal path: int8 levels; the general path does not use it: no
+     * load there) */
+    const int qpy = __builtin_amdgcn_readfirstlane((int)df.ep);
+    const QParams ql = g_qptab.q[qpy].l, qc = g_qptab.q[qpy].c;
     /* all the MB heads need of the NAL past this point: which of the 12 head
      * classes an MB takes (HeadSel).  The NAL's full context (NalCtx /
      * HeadCtx: ten more uniform values) is built again, from the argument
      * segment and the LDS waypoint table, only by the rare head over 128
      * bits (head_slow below) */
     const HeadSel HS = head_sel(S, a.nal[(size_t)s * a.ld_nal + df.nal]);
+    /* both sets of scalar loads are issued together and waited for here, in
+     * the shadow of the barrier, not behind it in front of the first
+     * transform (without the empty asm the compiler sinks them there) */
+    if (!general)
+        asm volatile(""
+                     :
+                     : "s"(HS.a_end), "s"(HS.mbw), "s"(ql.mf0), "s"(ql.mf1), "s"(ql.mf2), "s"(ql.qbits), "s"(ql.qf),
+                       "s"(qc.mf0), "s"(qc.mf1), "s"(qc.mf2), "s"(qc.qbits), "s"(qc.qf));
 
     /* ---- 1-2: records (levels -> CAVLC bodies) into LDS ---------------- */
     __syncthreads();                                    /* the row table (rt) */
@@ -1668,9 +1734,6 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
          * one mv): 0 or 4 here (k_dyn_rows sends half-pel chains to the
          * general path) */
         const uint32_t frc = __builtin_amdgcn_readfirstlane((L.rt[16] >> 28) & 7u);
-        /* the frame's rect QP (k_dyn_rows; QP_MIN and up here: int8 levels) */
-        const int qpy = __builtin_amdgcn_readfirstlane((int)df.ep);
-        const QParams ql = g_qptab.q[qpy].l, qc = g_qptab.q[qpy].c;
         /* round 6: a wave's passes are luma ones, then chroma ones, then
          * none (L0 and T are multiples of 64), so two loops whose kind is
          * known at compile time: no per-pass kind tests, and the compiler
@@ -1771,8 +1834,12 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             code_c(q + 1, B);
         }
         if (q < qC) code_c(q, A);
-        __syncthreads();                                /* levels, TotalCoeffs, ptabs, counts */
-        if (stp) stp[1] = __builtin_amdgcn_s_memrealtime();
+        /* the tables of the phases below, by the wave with the fewest level
+         * passes, while the others finish theirs (the pixel sets are dead:
+         * registers are free) */
+        if (wv0 == T - 64) row_copy_tabs(L, s, nb, lane);
+        __syncthreads();                                /* levels, TotalCoeffs, the tables, counts */
+        if (stp && t == 0) stp[1] = __builtin_amdgcn_s_memrealtime();
         /* the row's bottom TotalCoeffs (luma 12-15, chroma AC raster 2, 3 of
          * each plane) for the row below: one granule per MB */
         const bool nopub = DBG && (g.debug & SCROLL_DEBUG_DYN_NOPUBLISH) && s == 0 && f == 0 && r == 0;   /* tests */
@@ -1931,7 +1998,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         return a.bwd + (size_t)df.rbsp_bytes * (size_t)(NPC * ndt) + rec_of(r * w + k, pc, ndt);
     };
     __syncthreads();                                    /* records, top TotalCoeffs, waypoint table */
-    if (stp) stp[2] = __builtin_amdgcn_s_memrealtime();
+    if (stp && t == 0) stp[2] = __builtin_amdgcn_s_memrealtime();
 
     /* ---- 3: coeff_token, piece lengths ----------------------------------- */
     const Tabs &TB = g_tabs;
@@ -1982,7 +2049,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         token(i, k, pc, L.pcd[pc]);
     }
     __syncthreads();
-    if (stp) stp[3] = __builtin_amdgcn_s_memrealtime();
+    if (stp && t == 0) stp[3] = __builtin_amdgcn_s_memrealtime();
     const bool head_over = L.head_over;
     /* rare (a head over 128 bits has no class form): the NAL's HeadCtx again */
     auto head_slow = [&]() -> HeadCtx {
@@ -2101,7 +2168,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         }
         __syncthreads();
     }
-    if (stp) stp[4] = __builtin_amdgcn_s_memrealtime();
+    if (stp && t == 0) stp[4] = __builtin_amdgcn_s_memrealtime();
     const uint32_t bits = colpos(mbw);
     /* phase 5's own arguments, read here: no register held them (or a lane,
      * written and read back) through phases 1-4 */
@@ -2227,7 +2294,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         __syncthreads();
     }
     if (t == 0 && !lost) out[epc] = L.ncand;
-    if (stp) {
+    if (stp && t == 0) {
         stp[5] = __builtin_amdgcn_s_memrealtime();
         stp[6] = bits;
         stp[7] = (uint64_t)(uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 4);     /* HW_ID */
