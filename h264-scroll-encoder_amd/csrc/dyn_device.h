@@ -1168,10 +1168,17 @@ constexpr LvTab make_lvt()
  *     from them;
  *   - the level loop as in cavlc_body;
  *   - total_zeros + run_before as one field from the entry.
- * Same bits, TotalCoeff, TrailingOnes and ok as cavlc_body<CAP, true>. */
+ * Same bits, TotalCoeff, TrailingOnes and ok as cavlc_body<CAP, true>.
+ * With nC >= 0 and ct (the packed coeff_token tables, PTabs / RowTabs ct) the
+ * block's coeff_token at that context goes in front: TrailingOnes is known
+ * before the first level, so the token starts the accumulator and the whole
+ * piece is built in one go.  cap.n and ok then count the token too; a piece
+ * over 128 bits keeps its low 128 (the register loses top bits only), so a
+ * body of at most 128 bits is still whole in it. */
 template <class CAP>
 __device__ __host__ inline int cavlc_body_t(CAP &cap, const int8_t *lb, uint32_t nz, uint32_t tzrb, int &t1o,
-                                            bool &ok, const uint32_t *lvt)
+                                            bool &ok, const uint32_t *lvt, int nC = -1,
+                                            const uint16_t (*ct)[68] = nullptr)
 {
     const int tc = __builtin_popcount(nz);
     /* g: the mask shifted up one with a guard bit 0 -- clz(g) <= 31, and
@@ -1190,10 +1197,23 @@ __device__ __host__ inline int cavlc_body_t(CAP &cap, const int8_t *lb, uint32_t
     const int t1 = (int)o0 + (int)o1 + (int)o2;
     t1o = t1;
     ok = true;
-    if (tc == 0) return 0;
+    /* coeff_token of (tc, t1) at nC (Table 9-5; nC >= 8: six bits) */
+    uint32_t tv = 0u, tl = 0u;
+    if (nC >= 0) {
+        const uint32_t ce = ct[nC < 2 ? 0 : (nC < 4 ? 1 : 2)][4 * tc + t1];
+        tv = nC >= 8 ? (tc ? (uint32_t)(((tc - 1) << 2) | t1) : 3u) : (ce & 255u);
+        tl = nC >= 8 ? 6u : ce >> 8;
+    }
+    if (tc == 0) {
+        if (nC >= 0) {
+            cap.lo = tv;
+            cap.n = tl;
+        }
+        return 0;
+    }
     const uint32_t s3 = ((uint32_t)v0 >> 31) << 2 | ((uint32_t)v1 >> 31) << 1 | ((uint32_t)v2 >> 31);
-    uint64_t acc = s3 >> (3 - t1);                         /* the trailing-one signs, first one first */
-    uint32_t an = (uint32_t)t1;
+    uint64_t acc = (uint64_t)(tv << t1 | s3 >> (3 - t1));  /* the token, the trailing-one signs, first one first */
+    uint32_t an = tl + (uint32_t)t1;
     uint32_t g = t1 == 0 ? g0 : (t1 == 1 ? g1 : (t1 == 2 ? g2 : g3));      /* the levels left, over the guard bit */
     uint32_t m = g >> 1;
     auto push = [](uint64_t &ac, uint32_t &n, uint32_t v, uint32_t len, CAP &c) {

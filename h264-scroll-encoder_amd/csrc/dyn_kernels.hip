@@ -1214,8 +1214,12 @@ __device__ inline void put_piece1(uint32_t *buf, uint32_t pos, uint32_t tv, uint
  *      per MB (the row below waits for them: its top neighbours, the only
  *      hand-off between workgroups);
  *   2. counting sort on TotalCoeff, CAVLC bodies in that order (each
- *      wave's loop runs about its own blocks' count);
- *   3. coeff_token per piece from the left / top TotalCoeffs (nC);
+ *      wave's loop runs about its own blocks' count).  A piece whose top
+ *      neighbour is in this row has its nC from the sort's scatter on (both
+ *      neighbours' TotalCoeffs are in LDS): its body is coded coeff_token
+ *      first, and without levels it is its token, written by the scatter;
+ *   3. coeff_token of the 8 pieces per MB whose top neighbour is in the row
+ *      above (its granules), from the left / top TotalCoeffs (nC);
  *   4. per MB cbp, its code and the piece offsets; the row's MB offsets;
  *   5. the row's bits -> LDS window -> its own row-stage words, from bit 0
  *      (no position known yet: k_dyn_epfix places every row group), with
@@ -1263,7 +1267,8 @@ struct RowFixed {
         uint32_t buf[ROW_GB + 4];                /* + ROW_PAD: put_piece1's spare words */
         struct {
             uint32_t kc[2][SORT_KEYS];           /* the sort: blocks per TotalCoeff class, then its base */
-            uint32_t kc_pad[32 - 2 * SORT_KEYS];
+            uint32_t ovf;                        /* a body over 128 bits in the row (rare): its length after the records */
+            uint32_t kc_pad[31 - 2 * SORT_KEYS];
             uint32_t lvt[LVT_N];                 /* level codewords (CAVLC phase) */
         };
     };
@@ -1276,7 +1281,7 @@ struct RowFixed {
     uint32_t spill;                              /* its spill slot (a row over its slot) */
 };
 
-static_assert(2 * SORT_KEYS <= 32 && 32 + LVT_N <= ROW_GB, "the sort counts and the level table share the bit window");
+static_assert(2 * SORT_KEYS < 31 && 32 + LVT_N <= ROW_GB, "the sort counts, ovf and the level table share the bit window");
 static_assert(ROW_PAD == 4, "RowFixed::buf holds ROW_PAD spare words");
 static_assert(sizeof(RowFixed) <= 4992, "eight config-3 row workgroups per CU");
 
@@ -1489,14 +1494,6 @@ __device__ inline uint32_t bilin4(uint32_t b, uint32_t c, uint32_t f)
 static_assert(NPC == 26 && NPC * DYN_MAX_W < 18724, "div_npc's reciprocal (10083 / 2^18) is exact below 18724");
 __device__ inline int div_npc(int i) { return (int)(__umul24((uint32_t)i, 10083u) >> 18); }
 
-__device__ inline int row_slot(int task, int w)
-{
-    const int jj = task - 16 * w;                      /* < 0: luma */
-    const bool l = jj < 0;
-    const int k = l ? task >> 4 : jj >> 3, pc = l ? task & 15 : 18 + (jj & 7);
-    return (int)__umul24((uint32_t)k, (uint32_t)NPC) + pc;   /* no quarter-rate multiply */
-}
-
 /* k_dyn_row's arguments as ONE trivially-copyable struct: the kernel's only
  * parameter, so a field's offsetof is its offset in the kernel-argument
  * segment.  A uniform value named as a parameter is loaded in the entry
@@ -1704,6 +1701,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
      * done (it never has more of them than the others); the general path has
      * no levels and copies here. */
     if (t == 0) L.ncand = 0;
+    if (t == 0) L.ovf = 0u;
     if (t < SORT_KEYS) L.kc[0][t] = 0u;
     if (general && wv0 == T - 64) row_copy_tabs(L, s, nb, lane);
     /* the quantiser at the frame's rect QP (k_dyn_rows; QP_MIN and up on
@@ -1869,12 +1867,43 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             if (lane < SORT_KEYS) L.kc[1][lane] = kb - tot;
             wave_sync();
         }
+        /* The scatter, and nC where it is first known: an interior piece
+         * (top neighbour in this row: bit 13 of its class descriptor clear)
+         * has both neighbours' TotalCoeffs in LDS now, the popcounts of their
+         * masks -- no lane writes mt in this loop.  nC + 1 goes into lo's nC
+         * field (the rank was read from there just now; 0: a top-row piece,
+         * its token waits for the row above in phase 3) and the body lane puts
+         * the token in front of its body.  An interior block without levels
+         * has no body lane: its whole piece, the token of TotalCoeff 0, is
+         * written here (mt stays 0: the mask the neighbours read, and the
+         * right meta) */
+        const int nAs = g.x0 > 0 ? 0 : -1;
         for (int task = t; task < ntask; task += T) {       /* the slot, chroma flagged in bit 15 */
-            const int slot = row_slot(task, w);
+            const int jj = task - 16 * w;                   /* < 0: luma */
+            const bool l = jj < 0;
+            const int k = l ? task >> 4 : jj >> 3, pc = l ? task & 15 : 18 + (jj & 7);
+            const int slot = (int)__umul24((uint32_t)k, (uint32_t)NPC) + pc;   /* no quarter-rate multiply */
+            const uint32_t D = L.pcd[pc];
             const int tcs = __builtin_popcount(mt[slot]);
+            /* the top neighbour of an interior piece is in its own MB (a
+             * top-row piece's field is 0: itself, unused); the left one may
+             * be in the left MB, for MB 0 outside the rect */
+            const int ia = max(slot + (int)(D & 63u) - 32, 0), ib = slot + (int)((D >> 7) & 63u) - 32;
+            const int nB = __builtin_popcount(mt[ib]);
+            /* 9.2.1 as token() has it, nB always there: the rounded mean, or
+             * nB alone where the left neighbour is unavailable -- the mean of
+             * nB with itself */
+            const int nA = ((D & 64u) && k == 0) ? (nAs < 0 ? nB : 0) : __builtin_popcount(mt[ia]);
+            const int nC = (nA + nB + 1) >> 1;
+            const bool inner = !(D & 8192u);
             if (tcs) {
-                order[L.kc[1][SORT_KEYS - 1 - min(tcs, SORT_KEYS - 1)] + lo[slot]] =
-                    (uint16_t)(slot | (task < 16 * w ? 0 : 0x8000));
+                order[L.kc[1][SORT_KEYS - 1 - min(tcs, SORT_KEYS - 1)] + lo[slot]] = (uint16_t)(slot | (l ? 0 : 0x8000));
+                lo[slot] = (uint16_t)(inner ? (uint32_t)(nC + 1) << 11 : 0u);
+            } else if (inner) {
+                const uint32_t ce = L.ptabs.ct[nC < 2 ? 0 : (nC < 4 ? 1 : 2)][0];
+                const uint32_t tl = nC >= 8 ? 6u : ce >> 8, tv = nC >= 8 ? 3u : (ce & 255u);
+                reinterpret_cast<uint32_t *>(lv + slot)[0] = tv << (32u - tl);         /* its levels: all zero */
+                lo[slot] = (uint16_t)tl;                                                /* bare: nC field 0 */
             }
         }
         __syncthreads();
@@ -1893,10 +1922,37 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
              * during the trailing ones and the level loop */
             const uint32_t nz = mt[slot];                   /* the non-zero mask (levels phase) */
             const uint32_t tzrb = g_tzrb[luma ? nz : 65536u + nz];
-            const int tc = cavlc_body_t(cap, reinterpret_cast<const int8_t *>(lv + slot), nz, tzrb, t1, ok, L.lvt);
-            mt[slot] = ok ? (uint16_t)(cap.n | (uint32_t)tc << 8 | (uint32_t)t1 << 13)
-                          : (uint16_t)((uint32_t)tc << 8 | (uint32_t)t1 << 13 | M_OVF);
-            if (ok) lv[slot] = body_msb(cap.hi, cap.lo, cap.n);     /* else, rare: the levels stay */
+            /* the scatter's nC: an interior piece is coded token first and
+             * is then bare (lo = its length, nC field 0), as a chroma DC
+             * piece; -1: a top-row piece, its token in phase 3 (which writes
+             * lo) */
+            const int nC = (int)(lo[slot] >> 11) - 1;
+            const int tc = cavlc_body_t(cap, reinterpret_cast<const int8_t *>(lv + slot), nz, tzrb, t1, ok, L.lvt, nC,
+                                        L.ptabs.ct);
+            const uint32_t tm = (uint32_t)tc << 8 | (uint32_t)t1 << 13;
+            if (ok) {
+                mt[slot] = (uint16_t)(cap.n | tm);
+                lo[slot] = (uint16_t)cap.n;
+                lv[slot] = body_msb(cap.hi, cap.lo, cap.n);
+            } else {                                        /* rare */
+                uint32_t tv = 0, tl = 0;
+                if (nC >= 0) piece_token(L.ptabs.ct, tm, nC, tv, tl);
+                const uint32_t bn = cap.n - tl;
+                if (bn <= 128u) {
+                    /* over 128 bits only with its token: the register lost
+                     * top bits only, its low bn bits are the body -- stored
+                     * as a piece with its token not in front, phase 5 adds it */
+                    mt[slot] = (uint16_t)(bn | tm);
+                    lo[slot] = (uint16_t)(cap.n | (uint32_t)(nC + 1) << 11);
+                    lv[slot] = body_msb(cap.hi, cap.lo, bn);
+                } else {
+                    /* the body itself over 128 bits: the levels stay in lv,
+                     * the piece's length follows the records' barrier */
+                    mt[slot] = (uint16_t)(tm | M_OVF);
+                    lo[slot] = (uint16_t)((uint32_t)(nC + 1) << 11);
+                    L.ovf = 1u;
+                }
+            }
         }
         /* chroma DC blocks, whole (nC = -1): their slots (k NPC + 16 + p of
          * mt / lv) are no block task's, so nothing reads them before the
@@ -1917,9 +1973,12 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             const int tc = cavlc_dc4(cap, L.ptabs, dq);
             if (cap.n <= 128) {
                 mt[sl] = (uint16_t)(cap.n | (uint32_t)tc << 8);
+                lo[sl] = (uint16_t)cap.n;                             /* bare: its token is in the body */
                 lv[sl] = body_msb(cap.hi, cap.lo, cap.n);
             } else {
                 mt[sl] = (uint16_t)((uint32_t)tc << 8 | M_OVF);       /* the levels in lv */
+                lo[sl] = 0u;                                          /* nC -1; the length after the records' barrier */
+                L.ovf = 1u;
                 lv[sl] = make_uint4(((uint32_t)dq[0] & 0xffffu) | (uint32_t)dq[1] << 16,
                                     ((uint32_t)dq[2] & 0xffffu) | (uint32_t)dq[3] << 16, 0u, 0u);
             }
@@ -2044,9 +2103,29 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     /* phase 4's coded_block_pattern codes, entry `lane` in each lane (the
      * load is in flight during the tokens) */
     const uint32_t cbtab = TB.cbp_code[min(lane, 47)];
-    for (int i = t; i < npc; i += T) {
-        const int k = div_npc(i), pc = i - k * NPC;
-        token(i, k, pc, L.pcd[pc]);
+    if constexpr (GEN) {                                /* records without tokens: every piece */
+        for (int i = t; i < npc; i += T) {
+            const int k = div_npc(i), pc = i - k * NPC;
+            token(i, k, pc, L.pcd[pc]);
+        }
+    } else {
+        /* rare (uniform: the flag is written before the records' barrier):
+         * bodies over 128 bits among the interior and chroma DC pieces, their
+         * nC + 1 in lo -- the lengths, as token() takes a top-row one's */
+        if (L.ovf) {
+            for (int i = t; i < npc; i += T) {
+                const int k = div_npc(i), pc = i - k * NPC;
+                if (!(mt[i] & M_OVF) || (L.pcd[pc] & 8192u)) continue;
+                const uint32_t nc1 = (uint32_t)lo[i] >> 11;
+                lo[i] = (uint16_t)(ovf_bits(PT, TB, lv[i], nullptr, pc, (int)nc1 - 1) | nc1 << 11);
+            }
+        }
+        /* the 8 top-row pieces of every MB (luma 0-3, chroma AC 18, 19, 22,
+         * 23): their top neighbour is in the row above, its granules */
+        for (int i = t; i < 8 * w; i += T) {
+            const int k = i >> 3, j = i & 7, pc = j < 4 ? j : (j < 6 ? 14 + j : 16 + j);
+            token((int)__umul24((uint32_t)k, (uint32_t)NPC) + pc, k, pc, L.pcd[pc]);
+        }
     }
     __syncthreads();
     if (stp && t == 0) stp[3] = __builtin_amdgcn_s_memrealtime();
@@ -2276,9 +2355,12 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
             const int nC = (int)(e >> 11) - 1;
             const uint4 bd = lv[i];
             if (!(mv & M_OVF)) {
-                if (nC == -1) {                         /* a bare body (token in front since phase 3) */
-                    if (one) put_piece1(wb, pos, 0u, 0u, bd, mv & 255u);
-                    else put_piece(wb, p0, n, pos, 0u, 0u, bd, mv & 255u);
+                if (nC == -1) {
+                    /* a bare piece (token in front, or a chroma DC block):
+                     * its length is lo's -- an interior block without levels
+                     * is its token alone, mt 0 */
+                    if (one) put_piece1(wb, pos, 0u, 0u, bd, e & LO_LEN);
+                    else put_piece(wb, p0, n, pos, 0u, 0u, bd, e & LO_LEN);
                 } else {                                /* bodies over 128 - tl bits */
                     uint32_t tv = 0, tl = 0;
                     piece_token(ctab, mv, nC, tv, tl);

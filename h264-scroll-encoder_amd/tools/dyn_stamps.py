@@ -6,7 +6,8 @@ SCROLL_DEBUG_DYN_STAMPS and prints, per k_dyn_row workgroup (one rect row),
 the s_memrealtime span (100 MHz, microseconds) of each phase:
   levels       pixels -> residual -> transform -> quant, TotalCoeff ranks
   cavlc+poll   CAVLC bodies; the last wave polls the row above's TotalCoeffs
-  tokens       coeff_token and length of every piece
+  tokens       coeff_token and length of the 8 top-row pieces per MB (the
+               others have theirs since the CAVLC stretch)
   mb+scan      cbp, piece offsets per MB; the row's MB offsets
   write        bits -> LDS window -> the row's row-stage words
 plus the k_dyn_epfix steps and the k_dyn_gather workgroup spans.  Then times the workload
@@ -17,12 +18,19 @@ without stamps (HIP events).
 import argparse
 import ctypes
 import os
+import re
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+
+
+def static_rows():
+    """DYN_STATIC_ROWS as csrc/engine.h defines it (the MB rows of a static row group)"""
+    with open(os.path.join(os.path.dirname(HERE), "csrc", "engine.h")) as f:
+        return int(re.search(r"^#define\s+DYN_STATIC_ROWS\s+(\d+)", f.read(), re.M).group(1))
 
 
 def main():
@@ -55,7 +63,7 @@ def main():
     b.compose(F, rewind=True)
     assert b.sync() == 0, hs.last_error()
     mbh = H // 16
-    sr = 16                                        # DYN_STATIC_ROWS (engine.h)
+    sr = static_rows()
     na = max(1, -(-rect[1] // sr))
     ng = na + rect[3] + max(1, -(-(mbh - rect[1] - rect[3]) // sr))
     nslot = (2 + ng) * S * F
