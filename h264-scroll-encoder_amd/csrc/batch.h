@@ -6,6 +6,7 @@
  *   batch_rate.hip    the plain rect's per-frame QP table and the pick on the device
  *   batch_hint.hip    UI hints, the rect under hints, the splice
  *   batch_ingest.hip  ingest, I_PCM files, reference updates
+ *   batch_surface.hip pixels from RGBA / BGRA surfaces: the rect's source, I420 pictures, device references
  *   batch_dropin.hip  the synchronous drop-in helpers of engine.h
  * Nothing here enters the library's dynamic symbol table.
  */
@@ -121,6 +122,15 @@ struct ScrollBatch {
         hipEvent_t fin = nullptr;       /* recorded after the last pick's launch */
         int nframes = -1, nstreams = 0; /* the last pick; nframes -1: none */
     } rt;
+    /* pixels from renderer surfaces (batch_surface.hip, csc_kernels.hip):
+     * nothing here exists before the first conversion */
+    struct Surf {
+        int32_t *pos = nullptr;         /* [nstreams * nframes][2]: the last call's per-frame rect origins (custom positions only) */
+        std::vector<int32_t> h_pos;     /* what was uploaded there */
+        hipEvent_t fin = nullptr;       /* recorded after the last kernel that reads pos */
+        hipEvent_t ev[2] = {};          /* timing: around the last conversion (created on first use) */
+        int timed = 0;
+    } sf;
     /* UI hints: staged like the dynamic rect (shares
      * d_dfr, d_stage and geo.slot_bytes; the two are exclusive) */
     int hint_on = 0;
@@ -230,6 +240,7 @@ void probe_release(ScrollBatch *b);
 void dyn_release(ScrollBatch *b);
 int dyn_grow_pools(ScrollBatch *b);
 int dyn_reserve_gen(ScrollBatch *b, size_t need);
+int dyn_set_refs(ScrollBatch *b, int s, const uint8_t *ref_a, const uint8_t *ref_b, hipMemcpyKind kind);
 
 /* ---- batch_rate.hip ---- */
 void rate_release(ScrollBatch *b);
@@ -247,6 +258,11 @@ const char *splice_msg(int e);
 
 /* ---- batch_ingest.hip ---- */
 int ipcm_async_check(ScrollBatch *b);
+
+/* ---- batch_surface.hip ---- */
+/* the per-frame position table goes with the rect (all = false); the timing
+ * events with the batch (all = true) */
+void surface_release(ScrollBatch *b, bool all);
 
 }  // namespace batch
 }  // namespace scroll

@@ -540,6 +540,7 @@ void scroll_batch_destroy(ScrollBatch *b)
     probe_release(b);
     (void)hipFree(b->dx.qpf);
     rate_release(b);
+    surface_release(b, true);
     (void)hipFree(b->d_hf);
     (void)hipFree(b->d_pool);
     (void)hipFree(b->d_spf);

@@ -68,6 +68,7 @@ void dyn_release(ScrollBatch *b)
     (void)hipFree(b->dx.gbits);
     (void)hipFree(b->dx.qpf);          /* the per-frame QP table, its pick and the buckets' levels */
     rate_release(b);
+    surface_release(b, false);
     (void)hipFree(b->d_rec);           /* the reconstruction goes with the rect it was sized for */
     (void)hipFree(b->d_sse);
     b->d_rec = nullptr;
@@ -269,6 +270,42 @@ static int probe_run(ScrollBatch *b, int nframes, const ProbeQps &Q, void *hip_s
     return SCROLL_OK;
 }
 
+namespace scroll {
+namespace batch {
+
+/* reference pictures A and B of stream s (-1: of every stream) from host or
+ * device memory: scroll_batch_set_dyn_refs and _device */
+int dyn_set_refs(ScrollBatch *b, int s, const uint8_t *ref_a, const uint8_t *ref_b, hipMemcpyKind kind)
+{
+    if (!b || !b->dyn_on || !ref_a || !ref_b || s < -1 || s >= b->nstreams) return SCROLL_ERR_ARG;
+    int rc = batch_host_sync(b);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(b->device));
+    const bool dev = kind == hipMemcpyDeviceToDevice;
+    /* device pictures may come from work queued on any stream, and the copy
+     * from them must have landed before the next compose on any stream */
+    if (dev) HIPCHK(hipDeviceSynchronize());
+    const size_t pic = (size_t)3 * b->dyn_pw * b->dyn_ph / 2, pair = dyn_pair_bytes(b);
+    if (s >= 0 && b->dyn_refs == 1)                      /* shared -> per stream */
+        for (int k = 1; k < b->nstreams; ++k)
+            HIPCHK(hipMemcpy(b->d_refs + k * pair, b->d_refs, pair, hipMemcpyDeviceToDevice));
+    uint8_t *dst = b->d_refs + (s < 0 ? 0 : (size_t)s * pair);
+    HIPCHK(hipMemcpy(dst, ref_a, pic, kind));
+    HIPCHK(hipMemcpy(dst + pic, ref_b, pic, kind));
+    if (dev) HIPCHK(hipDeviceSynchronize());
+    if (s < 0) {
+        b->dyn_refs = 1;
+        b->geo.ref_ld = 0;
+    } else {
+        b->dyn_refs = 2;
+        b->geo.ref_ld = pair;
+    }
+    return SCROLL_OK;
+}
+
+}  // namespace batch
+}  // namespace scroll
+
 extern "C" {
 
 /* ------------------------------ dynamic rect ----------------------------- */
@@ -450,25 +487,7 @@ int scroll_batch_fallback_frame(ScrollBatch *b, int s, int f, int *fell_back)
 
 int scroll_batch_set_dyn_refs(ScrollBatch *b, int s, const uint8_t *ref_a, const uint8_t *ref_b)
 {
-    if (!b || !b->dyn_on || !ref_a || !ref_b || s < -1 || s >= b->nstreams) return SCROLL_ERR_ARG;
-    int rc = batch_host_sync(b);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(b->device));
-    const size_t pic = (size_t)3 * b->dyn_pw * b->dyn_ph / 2, pair = dyn_pair_bytes(b);
-    if (s >= 0 && b->dyn_refs == 1)                      /* shared -> per stream */
-        for (int k = 1; k < b->nstreams; ++k)
-            HIPCHK(hipMemcpy(b->d_refs + k * pair, b->d_refs, pair, hipMemcpyDeviceToDevice));
-    uint8_t *dst = b->d_refs + (s < 0 ? 0 : (size_t)s * pair);
-    HIPCHK(hipMemcpy(dst, ref_a, pic, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dst + pic, ref_b, pic, hipMemcpyHostToDevice));
-    if (s < 0) {
-        b->dyn_refs = 1;
-        b->geo.ref_ld = 0;
-    } else {
-        b->dyn_refs = 2;
-        b->geo.ref_ld = pair;
-    }
-    return SCROLL_OK;
+    return dyn_set_refs(b, s, ref_a, ref_b, hipMemcpyHostToDevice);
 }
 
 int scroll_batch_set_dyn_source(ScrollBatch *b, const uint8_t *src, int nframes)

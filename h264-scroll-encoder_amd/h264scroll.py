@@ -141,6 +141,18 @@ class ScrollDynRate(ctypes.Structure):
                 ("pad", ctypes.c_uint32)]
 
 
+SCROLL_SURF_RGBA, SCROLL_SURF_BGRA = 0, 1
+SCROLL_SURF_BT601, SCROLL_SURF_BT709 = 0, 1
+
+
+class ScrollSurfaces(ctypes.Structure):
+    """include/composer_batch.h: 8-bit RGBA / BGRA surfaces in device memory,
+    frame f of stream s at base + s stream_stride + f frame_stride"""
+    _fields_ = [("base", ctypes.c_void_p), ("pitch", ctypes.c_uint64), ("frame_stride", ctypes.c_uint64),
+                ("stream_stride", ctypes.c_uint64), ("format", ctypes.c_uint32), ("matrix", ctypes.c_uint32),
+                ("full_range", ctypes.c_uint32), ("cropped", ctypes.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} not built: run `make -C h264-scroll-encoder_amd` "
@@ -278,6 +290,14 @@ def _load():
                                                                 ctypes.c_void_p]),
         "scroll_batch_ipcm_stats": (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_double),
                                                    P(ctypes.c_int)]),
+        "scroll_batch_dyn_source_from_surfaces": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, P(ScrollSurfaces),
+                                                                 ctypes.c_void_p]),
+        "scroll_batch_surfaces_to_i420": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                         P(ScrollSurfaces), ctypes.c_void_p, ctypes.c_size_t,
+                                                         ctypes.c_void_p]),
+        "scroll_batch_set_dyn_refs_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                            ctypes.c_void_p]),
+        "scroll_batch_surface_ms": (ctypes.c_float, [ctypes.c_void_p]),
         "composer_batch_write_scroll_frames": (ctypes.c_int, [P(P(Composer)), P(ctypes.c_int),
                                                               ctypes.c_int, ctypes.c_int]),
         "composer_flush": (ctypes.c_int, [P(Composer)]),
@@ -441,6 +461,7 @@ class Batch:
         if rc != SCROLL_OK:
             raise RuntimeError(f"scroll_batch_create failed ({rc}): {last_error()}")
         self.h = h
+        self.max_streams = max_streams
         self.max_frames = max_frames
 
     def close(self):
@@ -710,6 +731,38 @@ class Batch:
         ls, lf = ctypes.c_size_t(), ctypes.c_size_t()
         p = lib.scroll_batch_dyn_source_device(self.h, ctypes.byref(ls), ctypes.byref(lf))
         return p, ls.value, lf.value
+
+    # ---- pixels from renderer surfaces ----
+    def dyn_source_from_surfaces(self, ptr, nframes, pitch, frame_stride, stream_stride=0, fmt=SCROLL_SURF_RGBA,
+                                 matrix=SCROLL_SURF_BT601, full_range=False, cropped=False, stream=None):
+        """frames 0 .. nframes - 1 of every stream's source from 8-bit RGBA /
+        BGRA surfaces in device memory (frame f of stream s at ptr + s
+        stream_stride + f frame_stride, rows pitch bytes apart): cut at each
+        frame's rect position, or cropped=True: the surfaces are the rect
+        itself.  Asynchronous on `stream` (scroll_batch_dyn_source_from_surfaces)"""
+        sf = ScrollSurfaces(ptr, pitch, frame_stride, stream_stride, fmt, matrix, 1 if full_range else 0,
+                            1 if cropped else 0)
+        self._chk(lib.scroll_batch_dyn_source_from_surfaces(self.h, nframes, ctypes.byref(sf), stream),
+                  "dyn_source_from_surfaces")
+
+    def surfaces_to_i420(self, n, w, h, ptr, pitch, frame_stride, d_pics, pic_stride, fmt=SCROLL_SURF_RGBA,
+                         matrix=SCROLL_SURF_BT601, full_range=False, stream=None):
+        """n whole w x h surfaces at ptr + i frame_stride -> I420 pictures at
+        d_pics + i pic_stride (device; what ipcm_files_device and
+        set_dyn_refs_device read).  Asynchronous on `stream`"""
+        sf = ScrollSurfaces(ptr, pitch, frame_stride, 0, fmt, matrix, 1 if full_range else 0, 0)
+        self._chk(lib.scroll_batch_surfaces_to_i420(self.h, n, w, h, ctypes.byref(sf), ctypes.c_void_p(d_pics),
+                                                    pic_stride, stream), "surfaces_to_i420")
+
+    def set_dyn_refs_device(self, a_ptr, b_ptr, stream=-1):
+        """set_dyn_refs with the I420 pictures in device memory"""
+        self._chk(lib.scroll_batch_set_dyn_refs_device(self.h, stream, ctypes.c_void_p(a_ptr),
+                                                       ctypes.c_void_p(b_ptr)), "set_dyn_refs_device")
+
+    def surface_ms(self):
+        """with enable_timing: HIP-event ms of the last surface conversion's
+        launches (-1 without)"""
+        return lib.scroll_batch_surface_ms(self.h)
 
     def dyn_source_synth(self, nframes, stream_base=0, t0=0):
         self._chk(lib.scroll_batch_dyn_source_synth(self.h, nframes, stream_base, t0),

@@ -721,6 +721,86 @@ int scroll_batch_ipcm_files_device_async(ScrollBatch *b, int n, int w, int h, co
  * call (both passes) and the number of calls */
 int scroll_batch_ipcm_stats(ScrollBatch *b, double *ms, int *count);
 
+/* ---- pixels from renderer surfaces (docs/MASTER_DESIGN.md §5: "dynamic-region
+ * pixels for frame N (cropped from renderer)") ----
+ * A renderer hands out 8-bit RGBA or BGRA framebuffers; the rect's source,
+ * the references and the I_PCM writer above take planar I420.  These calls
+ * crop, convert and subsample on the device, by one exact integer rule
+ * (csrc/csc_device.h; alpha ignored):
+ *     Y = (yr R + yg G + yb B + yoff) >> 16                         per pixel
+ *     C = clamp((cr Sr + cg Sg + cb Sb + (128 << 18) + (1 << 17)) >> 18, 0, 255)
+ * per 2x2 quad, Sr Sg Sb the quad's channel sums (box siting: the chroma
+ * sample sits at the quad's centre), Q16 coefficients of BT.601 or BT.709 in
+ * limited (16..235 / 16..240) or full range.  Every output is within 0.506
+ * of the real-valued matrix.
+ *
+ * ScrollSurfaces: frame f of stream s is the surface at base + s
+ * stream_stride + f frame_stride, rows pitch bytes apart, 4 bytes per pixel.
+ * base, pitch and both strides are multiples of 16 (every load is then a full
+ * 16-byte vector load); pitch covers the surface's width.
+ *
+ *   scroll_batch_dyn_source_from_surfaces(b, nframes, &surf, hip_stream)
+ *       fills frames 0 .. nframes - 1 of every stream of the source buffer
+ *       (scroll_batch_set_dyn_source's, scroll_batch_dyn_source_device's
+ *       layout).  cropped = 0: the surfaces are whole pictures and frame f of
+ *       stream s is cut out where its rect sits -- scroll_batch_set_dyn_rect's
+ *       position, or scroll_batch_set_dyn_rect_at's; cropped = 1: they are the
+ *       rect itself, 16w x 16h pixels.  A frame without a rect (set_dyn_rect_at
+ *       with x0 = -1) and frames from nframes on keep their bytes -- except
+ *       with the fallback on (scroll_batch_set_fallback): there a frame
+ *       without the rect is coded as the whole picture from its source block
+ *       if it falls back, which only the compose decides, so it is converted
+ *       like a frame with the rect at (0, 0) (the rect is the whole picture).
+ *       Asynchronous on hip_stream (0 = the batch's own), which must be the
+ *       stream of the probe or compose that reads the source.  The batch's
+ *       host-side calls do not wait for it: synchronise hip_stream before a
+ *       scroll_batch_set_dyn_source / _synth into the same buffer and
+ *       before the surfaces are rewritten or freed.  With per-frame
+ *       positions the call first waits for the
+ *       previous such call's kernel (it uploads a table of them).
+ *       SCROLL_ERR_CONFIG without a dynamic rect; SCROLL_ERR_ARG, and nothing
+ *       written, for a misaligned base, pitch or stride, an unknown format or
+ *       matrix, nframes outside 0..max_frames, a pitch smaller than the
+ *       surface's row, or more than 2^35 pixels in one call.
+ *   scroll_batch_surfaces_to_i420(b, n, w, h, &surf, d_pics, pic_stride, hip_stream)
+ *       n whole w x h surfaces (multiples of 16) at base + i frame_stride
+ *       become I420 pictures at d_pics + i pic_stride (Y w*h, then Cb, Cr
+ *       w*h/4 each; d_pics and pic_stride multiples of 16): what
+ *       scroll_batch_ipcm_files_device and scroll_batch_set_dyn_refs_device
+ *       read.  stream_stride and cropped are ignored.  Needs no dynamic rect.
+ *       Asynchronous on hip_stream: scroll_batch_ipcm_files_device runs on the
+ *       batch's own stream, so synchronise hip_stream first unless it is that
+ *       one (0).  At most 2^35 pixels per call (SCROLL_ERR_ARG).
+ *   scroll_batch_set_dyn_refs_device(b, s, d_ref_a, d_ref_b)
+ *       scroll_batch_set_dyn_refs with the pictures in device memory (a
+ *       device-to-device copy, the same shared / per-stream semantics;
+ *       synchronous), so pictures go from renderer surfaces to the coder's
+ *       references without a host step.
+ *   scroll_batch_surface_ms(b)   with scroll_batch_enable_timing: HIP-event ms
+ *       of the last conversion's launches; -1 without.
+ * A compose that uses none of these gains no launch, allocation or changed
+ * byte. */
+#define SCROLL_SURF_RGBA  0         /* bytes in memory: R, G, B, A */
+#define SCROLL_SURF_BGRA  1         /* bytes in memory: B, G, R, A */
+#define SCROLL_SURF_BT601 0
+#define SCROLL_SURF_BT709 1
+typedef struct {
+    const uint8_t *base;        /* device memory */
+    uint64_t pitch;             /* bytes per pixel row */
+    uint64_t frame_stride;      /* bytes between a stream's consecutive frames */
+    uint64_t stream_stride;     /* bytes between streams; 0: every stream reads the same surfaces */
+    uint32_t format;            /* SCROLL_SURF_RGBA / SCROLL_SURF_BGRA */
+    uint32_t matrix;            /* SCROLL_SURF_BT601 / SCROLL_SURF_BT709 */
+    uint32_t full_range;        /* 0 limited (16..235 / 16..240), 1 full */
+    uint32_t cropped;           /* 0: surfaces are whole pictures, the rect is cut out at each frame's rect
+                                   position; 1: surfaces are the rect itself, 16w x 16h pixels */
+} ScrollSurfaces;
+int scroll_batch_dyn_source_from_surfaces(ScrollBatch *b, int nframes, const ScrollSurfaces *surf, void *hip_stream);
+int scroll_batch_surfaces_to_i420(ScrollBatch *b, int n, int w, int h, const ScrollSurfaces *surf,
+                                  uint8_t *d_pics, size_t pic_stride, void *hip_stream);
+int scroll_batch_set_dyn_refs_device(ScrollBatch *b, int s, const uint8_t *d_ref_a, const uint8_t *d_ref_b);
+float scroll_batch_surface_ms(ScrollBatch *b);   /* with enable_timing; -1 without */
+
 /* Composer-level batch: offsets[i] composed on cs[i], i < n, in
  * order; Composers may repeat.  Output lands in each Composer's buffer before
  * return (equivalent to n composer_write_scroll_frame calls + a flush). */
