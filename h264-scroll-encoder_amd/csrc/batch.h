@@ -158,6 +158,18 @@ struct ScrollBatch {
     DynFork fork{};                    /* SCROLL_DYN_FORK=1: the general path + static groups beside k_dyn_row */
     std::vector<int32_t> h_dyn_qp;     /* [s * max_frames + f]: the frame's rect QP under hints, -1: the stream's */
     int dyn_pos_custom = 0;            /* some frame's origin differs from the batch rect */
+    /* scroll_batch_set_dyn_rect_moving: h_dyn_pos honoured without hints, on
+     * the k_dyn_row path.  The device table (DynGeom.dpos's form) exists
+     * while the flag is on and is uploaded, on the stream of the compose or
+     * probe that finds it stale, only while some entry differs from the
+     * batch's position; otherwise the kernels get no table */
+    int dyn_moving = 0;
+    uint32_t *d_dpos = nullptr;        /* [max_streams * max_frames] */
+    std::vector<uint32_t> h_dpos;      /* what was uploaded there (the copy's source until the stream has run it) */
+    int dpos_stale = 1;                /* h_dyn_pos changed since the upload */
+    int dpos_any = 0;                  /* as of the upload: some entry differs */
+    hipStream_t dpos_hs = nullptr;     /* the stream that upload ran on ... */
+    hipEvent_t dpos_ev = nullptr;      /* ... and its end: other streams wait for it, the next packing too */
     int dyn_qp = 26;                   /* the rect's QP (scroll_batch_set_dyn_qp)          */
     int hd_dirty = 0;                  /* d_spf / HintFrame of the combined frames out of date */
     uint32_t hd_mb_words = 0;          /* pool words per rect MB */
@@ -241,6 +253,10 @@ void dyn_release(ScrollBatch *b);
 int dyn_grow_pools(ScrollBatch *b);
 int dyn_reserve_gen(ScrollBatch *b, size_t need);
 int dyn_set_refs(ScrollBatch *b, int s, const uint8_t *ref_a, const uint8_t *ref_b, hipMemcpyKind kind);
+/* *dpos: the position table for a launch of the plain rect's kernels on hs
+ * (uploaded there first when stale), or NULL: the flag is off, or every
+ * frame sits at the batch's position */
+int dyn_pos_table(ScrollBatch *b, hipStream_t hs, const uint32_t **dpos);
 
 /* ---- batch_rate.hip ---- */
 void rate_release(ScrollBatch *b);

@@ -266,14 +266,17 @@ int launch(ScrollBatch *b, int nframes, int plan_mode, int nal_max, hipStream_t 
         if ((rc = mark(1)) || (rc = mark(2)) || (rc = mark(3))) return rc;
     } else {
         const bool dyn_rect = b->dyn_on && !hint;
+        /* moving rects: the position table for this compose's kernels (NULL: none set, or hints) */
+        b->geo.dpos = nullptr;
+        if (dyn_rect && b->dyn_moving && (rc = dyn_pos_table(b, hs, &b->geo.dpos))) return rc;
         scroll_launch_plan(hs, S, b->d_st, b->d_off, b->max_frames, b->d_nal, b->ld_nal, nframes, plan_mode,
                            plan_debug | plan_flags | PLAN_STATE | PLAN_DYN, b->d_pend, b->d_dfr,
-                           ld_fr, nullptr, 0u, 0u, dyn_rect ? b->dx.ctr : nullptr);
+                           ld_fr, nullptr, 0u, 0u, dyn_rect ? b->dx.ctr : nullptr, b->geo.dpos);
         HIPCHK(hipGetLastError());
         if ((rc = mark(1))) return rc;
         uint64_t *stamps = nullptr;
         if (b->debug & SCROLL_DEBUG_DYN_STAMPS) {   /* k_dyn_emit_gather's, then k_dyn_group's */
-            const size_t slots = (2 + (size_t)b->geo.ngroups) * (size_t)nframes * S;
+            const size_t slots = (2 + (size_t)b->geo.ld_groups) * (size_t)nframes * S;
             if ((rc = dbg_stamps(b, slots, hs))) return rc;
             stamps = b->d_dbg + 2 * (size_t)nframes * S * 8;
         }
@@ -384,7 +387,7 @@ int launch(ScrollBatch *b, int nframes, int plan_mode, int nal_max, hipStream_t 
         scroll_launch_plan(hs, S, b->d_st, b->d_off, b->max_frames, b->d_nal, b->ld_nal, nframes, plan_mode,
                            plan_debug | plan_flags | PLAN_SIZE | PLAN_DYN, b->d_pend, b->d_dfr,
                            ld_fr, (b->dyn_on && !b->hint_on) ? (const uint32_t *)b->dx.ctr : nullptr,
-                           b->geo.rs_spill_cap, b->geo.gen_cap);
+                           b->geo.rs_spill_cap, b->geo.gen_cap, nullptr, b->geo.dpos);
         HIPCHK(hipGetLastError());
         if ((rc = mark(3))) return rc;
     }
@@ -694,7 +697,7 @@ int scroll_batch_compose_ex(ScrollBatch *b, int nframes, void *hip_stream, int f
     }
     HIPCHK(hipSetDevice(b->device));
     const bool combined = b->hint_on && b->dyn_on;
-    if (b->dyn_pos_custom && !b->hint_on) {
+    if (b->dyn_pos_custom && !b->hint_on && !b->dyn_moving) {
         set_err("scroll_batch_compose: per-frame dynamic rect positions need UI hints "
                 "(scroll_batch_set_hints)");
         return SCROLL_ERR_CONFIG;

@@ -67,6 +67,15 @@ void dyn_release(ScrollBatch *b)
     (void)hipFree(b->dx.ctr);
     (void)hipFree(b->dx.gbits);
     (void)hipFree(b->dx.qpf);          /* the per-frame QP table, its pick and the buckets' levels */
+    (void)hipFree(b->d_dpos);          /* the moving rect's position table goes with the rect */
+    if (b->dpos_ev) (void)hipEventDestroy(b->dpos_ev);
+    b->d_dpos = nullptr;
+    b->dpos_ev = nullptr;
+    b->dpos_hs = nullptr;
+    b->h_dpos.clear();
+    b->dyn_moving = 0;
+    b->dpos_stale = 1;
+    b->dpos_any = 0;
     rate_release(b);
     surface_release(b, false);
     (void)hipFree(b->d_rec);           /* the reconstruction goes with the rect it was sized for */
@@ -258,9 +267,12 @@ static int probe_run(ScrollBatch *b, int nframes, const ProbeQps &Q, void *hip_s
         if (timed) HIPCHK(hipEventRecord(p.ev[0], hs));
         DynGeom G = b->geo;
         G.debug = b->debug;
+        /* moving rects (never under hints): the frames' own origins, and no dynamic NAL where there is no rect */
+        int prc = dyn_pos_table(b, hs, &G.dpos);
+        if (prc) return prc;
         const int plan = b->mode == SCROLL_MODE_EXPERIMENT ? SCROLL_PLAN_EXPERIMENT : SCROLL_PLAN_COMPOSER;
         scroll_launch_plan(hs, S, b->d_st, b->d_off, b->max_frames, p.nal, b->ld_nal, nframes, plan,
-                           b->debug | PLAN_STATE | PLAN_DYN, p.pend, p.dfr, ld_fr, nullptr, 0u, 0u, ctr);
+                           b->debug | PLAN_STATE | PLAN_DYN, p.pend, p.dfr, ld_fr, nullptr, 0u, 0u, ctr, G.dpos);
         HIPCHK(hipGetLastError());
         const int rc = own(hs, S, G, timed ? p.ev[1] : nullptr);
         if (rc) return rc;
@@ -300,6 +312,36 @@ int dyn_set_refs(ScrollBatch *b, int s, const uint8_t *ref_a, const uint8_t *ref
         b->dyn_refs = 2;
         b->geo.ref_ld = pair;
     }
+    return SCROLL_OK;
+}
+
+int dyn_pos_table(ScrollBatch *b, hipStream_t hs, const uint32_t **dpos)
+{
+    *dpos = nullptr;
+    if (!b->dyn_on || !b->dyn_moving || b->hint_on) return SCROLL_OK;
+    if (b->dpos_stale) {
+        /* the last upload has read its source */
+        if (b->dpos_hs) HIPCHK(hipEventSynchronize(b->dpos_ev));
+        const size_t n = (size_t)b->max_streams * b->max_frames;
+        b->h_dpos.resize(n);
+        bool any = false;
+        for (size_t i = 0; i < n; ++i) {
+            const int32_t x = b->h_dyn_pos[2 * i], y = b->h_dyn_pos[2 * i + 1];
+            any |= x != b->geo.x0 || (x >= 0 && y != b->geo.y0);
+            b->h_dpos[i] = x < 0 ? DYN_POS_NONE : (uint32_t)x | (uint32_t)y << 16;
+        }
+        b->dpos_hs = nullptr;
+        if (any) {
+            HIPCHK(hipMemcpyAsync(b->d_dpos, b->h_dpos.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, hs));
+            HIPCHK(hipEventRecord(b->dpos_ev, hs));
+            b->dpos_hs = hs;
+        }
+        b->dpos_any = any ? 1 : 0;
+        b->dpos_stale = 0;
+    }
+    if (!b->dpos_any) return SCROLL_OK;
+    if (hs != b->dpos_hs) HIPCHK(hipStreamWaitEvent(hs, b->dpos_ev, 0));   /* uploaded on another stream */
+    *dpos = b->d_dpos;
     return SCROLL_OK;
 }
 
@@ -350,17 +392,12 @@ int scroll_batch_set_dyn_rect(ScrollBatch *b, int x0, int y0, int w, int h, size
     g.qp = b->dyn_qp;
     g.ql = scroll::dyn::qparams(g.qp);
     g.qc = scroll::dyn::qparams(scroll::dyn::qp_chroma(g.qp));
-    {
-        const int sr = DYN_STATIC_ROWS;
-        const int na = (y0 + sr - 1) / sr, nbl = (mbh - y0 - h + sr - 1) / sr;
-        g.ngroups = (na > 1 ? na : 1) + h + (nbl > 1 ? nbl : 1);
-    }
     g.src_fr = (uint64_t)384 * w * h;
     g.src_ld = round256((size_t)b->max_frames * g.src_fr);
     g.ref_ld = 0;
     g.slot_bytes = slot_bytes ? round256(slot_bytes + DYN_OVF_BYTES) : dyn_slot_bound(mbw, mbh, w, h);
     g.ep_cap = dyn_ep_cap(w, h, b->debug);
-    dyn_rowstage_geom(&g, mbw, mbh);
+    dyn_rowstage_geom(&g, mbw, mbh, 0);                /* ngroups = ld_groups: this placement's */
     b->dyn_pw = pw;
     b->dyn_ph = ph;
     const size_t S = (size_t)b->max_streams, F = (size_t)b->max_frames;
@@ -394,7 +431,7 @@ int scroll_batch_set_dyn_rect(ScrollBatch *b, int x0, int y0, int w, int h, size
     if (e == hipSuccess) e = hipMalloc(&b->dx.body_lo, nrec * sizeof(uint2));
     if (e == hipSuccess) e = hipMalloc(&b->dx.body_hi, nrec * sizeof(uint2));
     if (e == hipSuccess) e = hipMalloc(&b->dx.body_w, nrec * sizeof(uint4));
-    const size_t ng = (size_t)g.ngroups;
+    const size_t ng = (size_t)g.ld_groups;
     if (e == hipSuccess) e = hipMalloc(&b->dx.heads, S * F * DYN_HEAD_VECS * sizeof(uint4));
     if (e == hipSuccess) e = hipMalloc(&b->dx.tcx, S * F * w * h * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(b->dx.tcx, 0, S * F * w * h * sizeof(unsigned long long));
@@ -444,12 +481,70 @@ int scroll_batch_set_dyn_rect_at(ScrollBatch *b, int s, int f, int x0, int y0)
     }
     int rc = batch_host_sync(b);
     if (rc) return rc;
+    /* with moving rects a probe on a stream of its own may still read the device table */
+    if (b->dyn_moving && b->pb.fin) HIPCHK(hipEventSynchronize(b->pb.fin));
     const size_t i = (size_t)s * b->max_frames + f;
     b->h_dyn_pos[2 * i] = x0 < 0 ? -1 : x0;
     b->h_dyn_pos[2 * i + 1] = x0 < 0 ? -1 : y0;
     if (x0 != b->geo.x0 || (x0 >= 0 && y0 != b->geo.y0)) b->dyn_pos_custom = 1;
+    b->dpos_stale = 1;
     b->hd_dirty = 1;
     b->hint_dirty = 1;
+    return SCROLL_OK;
+}
+
+/* The plain rect placed per stream and per frame: on, a
+ * compose without hints honours scroll_batch_set_dyn_rect_at's positions on
+ * the k_dyn_row path.  A frame's row groups change in number with y0, so the
+ * row stage (every frame's region, the static groups' slots) and the groups'
+ * bit counts are sized here, once, for every legal y0: no later position
+ * allocates.  Off: back to the batch position's sizes.  The flag goes with
+ * the rect (scroll_batch_set_dyn_rect drops it). */
+int scroll_batch_set_dyn_rect_moving(ScrollBatch *b, int on)
+{
+    if (!b) return SCROLL_ERR_ARG;
+    if (!b->dyn_on) {
+        if (!on) return SCROLL_OK;
+        set_err("scroll_batch_set_dyn_rect_moving: needs a dynamic rect (scroll_batch_set_dyn_rect)");
+        return SCROLL_ERR_CONFIG;
+    }
+    if ((on != 0) == (b->dyn_moving != 0)) return SCROLL_OK;
+    int rc = batch_host_sync(b);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(b->device));
+    if (b->pb.fin) HIPCHK(hipEventSynchronize(b->pb.fin));     /* a probe on another stream */
+    if (b->dpos_ev) HIPCHK(hipEventSynchronize(b->dpos_ev));
+    DynGeom g = b->geo;
+    dyn_rowstage_geom(&g, b->dyn_pw / 16, b->dyn_ph / 16, on ? 1 : 0);
+    const size_t S = (size_t)b->max_streams, F = (size_t)b->max_frames;
+    const size_t rs_words = S * F * g.rs_frame_words + (size_t)g.rs_spill_cap * g.rs_spill_words;
+    uint32_t *rs = nullptr, *gbits = nullptr, *dpos = nullptr;
+    hipEvent_t ev = nullptr;
+    hipError_t e = hipMalloc(&rs, rs_words * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&gbits, S * F * (size_t)g.ld_groups * sizeof(uint32_t));
+    if (e == hipSuccess && on) e = hipMalloc(&dpos, S * F * sizeof(uint32_t));
+    if (e == hipSuccess && on) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        (void)hipFree(rs);
+        (void)hipFree(gbits);
+        (void)hipFree(dpos);
+        return hip_fail("scroll_batch_set_dyn_rect_moving", e, true);
+    }
+    (void)hipFree(b->dx.rowstage);
+    (void)hipFree(b->dx.gbits);
+    (void)hipFree(b->d_dpos);
+    if (b->dpos_ev) (void)hipEventDestroy(b->dpos_ev);
+    b->dx.rowstage = rs;
+    b->dx.spill = rs + S * F * g.rs_frame_words;
+    b->dx.gbits = gbits;
+    b->d_dpos = dpos;
+    b->dpos_ev = ev;
+    b->dpos_hs = nullptr;
+    b->dpos_stale = 1;
+    b->dpos_any = 0;
+    g.dpos = nullptr;
+    b->geo = g;
+    b->dyn_moving = on ? 1 : 0;
     return SCROLL_OK;
 }
 
@@ -513,7 +608,11 @@ int scroll_batch_dyn_source_synth(ScrollBatch *b, int nframes, int stream_base, 
 {
     if (!b || !b->dyn_on || nframes < 0 || nframes > b->max_frames) return SCROLL_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
-    if (dyn_launch_synth(b->own, nframes, b->nstreams, b->d_src, &b->geo, stream_base, t0)) {
+    /* with moving rects every frame's pattern is the one of its own position (a frame without a rect: the origin's) */
+    DynGeom G = b->geo;
+    int rc = dyn_pos_table(b, b->own, &G.dpos);
+    if (rc) return rc;
+    if (dyn_launch_synth(b->own, nframes, b->nstreams, b->d_src, &G, b->max_frames, stream_base, t0)) {
         set_err("k_dyn_synth launch: %s", hipGetErrorString(hipGetLastError()));
         return SCROLL_ERR_HIP;
     }

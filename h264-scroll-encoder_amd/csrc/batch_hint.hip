@@ -360,6 +360,7 @@ int scroll_batch_clear_hints(ScrollBatch *b)
                 b->h_dyn_pos[2 * i + 1] = b->geo.y0;
             }
             b->dyn_pos_custom = 0;
+            b->dpos_stale = 1;
         }
     }
     return SCROLL_OK;

@@ -82,11 +82,14 @@ int dyn_launch_emit(hipStream_t hs, int nframes, int S, const DevStream *st, con
                     int ld_nal, const DynFrame *dfr, int ld_fr, const DynGeom *g,
                     const uint8_t *stage, const DynScratch *x, uint8_t *arena, uint64_t ld_arena,
                     uint64_t *stamps);
-int dyn_launch_synth(hipStream_t hs, int nframes, int S, uint8_t *src, const DynGeom *g,
+/* ld_fr: the position table's frames per stream (g->dpos, where set) */
+int dyn_launch_synth(hipStream_t hs, int nframes, int S, uint8_t *src, const DynGeom *g, int ld_fr,
                      int stream_base, int t0);
 
-/* row-stage geometry (rs_* fields) of a rect in an mbw x mbh picture */
-void dyn_rowstage_geom(DynGeom *g, int mbw, int mbh);
+/* row groups (ngroups, ld_groups) and row-stage geometry (rs_* fields) of a
+ * rect in an mbw x mbh picture; moving: sized for every legal y0 (ld_groups
+ * the most groups of any, a static group's slot for the most rows of any) */
+void dyn_rowstage_geom(DynGeom *g, int mbw, int mbh, int moving);
 /* staging bytes per frame that no dynamic NAL can exceed */
 size_t dyn_slot_bound(int mbw, int mbh, int rw, int rh);
 /* EP positions kept per frame for an rw x rh MB rect on the rows' path

@@ -34,6 +34,7 @@
 
 #include "dyn_device.h"
 #include "dyn_engine.h"
+#include "dyn_pos.h"
 #include "nal_ctx.h"
 #include "stage_util.h"
 
@@ -269,6 +270,7 @@ __device__ inline void code_frame(const DevStream *__restrict__ st,
     const int lane = t & 63, wave = t >> 6;
     const DynFrame df = dfr[(size_t)s * ld_fr + f];
     if (df.nal < 0 || !(df.err & DF_GENERAL)) return;
+    dyn_frame_geom(g, (size_t)s * ld_fr + f);           /* the frame's own origin */
     load_ptabs(ptabs, t, CODE_T);
     if (t < 8) {
         wo[t] = pend[s].wo[t];
@@ -823,6 +825,7 @@ __global__ __launch_bounds__(256) void k_dyn_rows(const DevStream *__restrict__ 
     DynFrame *DF = dfr + (size_t)s * ld_fr + f;
     const int j = DF->nal;
     if (j < 0) return;
+    dyn_frame_geom(g, (size_t)s * ld_fr + f);           /* the prediction rows of the frame's own rect */
     if (t < 8) {
         wo[t] = pend[s].wo[t];
         wl[t] = pend[s].wl[t];
@@ -934,14 +937,23 @@ __global__ __launch_bounds__(GW) void k_dyn_static(const DevStream *__restrict__
 {
     __shared__ StaticFixed L;
     constexpr int SR = DYN_STATIC_ROWS;
-    const Rect R{g.x0, g.y0, g.w, g.h};
-    const int nA = max(1, (R.y0 + SR - 1) / SR);
-    const int gi = (int)blockIdx.x >= nA ? (int)blockIdx.x + R.h : (int)blockIdx.x;
-    const int ng = g.ngroups, f = blockIdx.y, s = blockIdx.z, t = threadIdx.x;
+    const int f = blockIdx.y, s = blockIdx.z, t = threadIdx.x;
     const size_t nb = (size_t)s * ld_fr + f;
     const DynFrame df = dfr[nb];
     const int j = df.nal;
     if (j < 0) return;
+    /* the grid is ld_groups - h wide: the most static groups of any
+     * placement.  A frame whose own placement has fewer leaves the rest
+     * with a zero bit count (trailing groups nobody reads past) */
+    dyn_frame_geom(g, nb);
+    const Rect R{g.x0, g.y0, g.w, g.h};
+    const int nA = max(1, (R.y0 + SR - 1) / SR);
+    const int gi = (int)blockIdx.x >= nA ? (int)blockIdx.x + R.h : (int)blockIdx.x;
+    const int ng = g.ngroups;
+    if (gi >= ng) {
+        if (t == 0) gbits[nb * (size_t)g.ld_groups + gi] = 0u;
+        return;
+    }
     const bool first = gi == 0, last = gi == ng - 1;
     if (t < 8) {
         L.wo[t] = pend[s].wo[t];
@@ -1010,7 +1022,7 @@ __global__ __launch_bounds__(GW) void k_dyn_static(const DevStream *__restrict__
     const uint32_t rows_end = F + __shfl(incl, GW - 1, GW);
     if (t == 0) L.moff[rb - ra] = rows_end;
     const uint32_t bits = rows_end + (last ? 1u : 0u);
-    if (t == 0) gbits[nb * (size_t)ng + gi] = bits;
+    if (t == 0) gbits[nb * (size_t)g.ld_groups + gi] = bits;
     wave_sync();
 
     uint32_t *out = rowstage + nb * g.rs_frame_words + rs_group_words(g, nA, gi);
@@ -1514,6 +1526,7 @@ struct RowArgs {
     const uint4 *heads;
     int32_t ld_nal, ld_fr;
     DynGeom g;                  /* named: the rect, pw / ph, the source / reference strides */
+    uint64_t pad1;              /* (tcx on a 16-byte boundary) */
     /* the hand-off: the publish after the levels, the poll before phase 3 */
     unsigned long long *tcx;
     uint32_t epoch, pad0;
@@ -1600,12 +1613,20 @@ __device__ inline void row_copy_tabs(RowFixed &L, int s, size_t nb, int lane)
  * other's code (registers).  DBG: the instantiations with the per-phase
  * stamps (tools/dyn_stamps.py) and the tests' NOPUBLISH hook, launched only
  * when either is on: the product ones hold none of that state */
-template <bool GEN, bool DBG>
+/* POS: the instantiations for a compose with a position table (g.dpos,
+ * scroll_batch_set_dyn_rect_moving), launched only then: the frame's origin
+ * comes by one scalar load at the head, issued with the DynFrame's, and takes
+ * the place of the argument's x0, y0 -- two uniform values for two.  The
+ * pixel loads' offsets hold x0, so they wait for it (a round trip the other
+ * instantiations do not have; they never test the pointer) */
+template <bool GEN, bool DBG, bool POS>
 __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL_ROW_WAVES))) void k_dyn_row(const RowArgs a)
 {
     __shared__ RowFixed L;
     extern __shared__ uint4 rdyn[];
-    const DynGeom &g = a.g;
+    DynGeom gp;                         /* POS: the argument with the frame's origin */
+    if (POS) gp = a.g;
+    const DynGeom &g = POS ? gp : a.g;
     /* debug: realtime at entry and after each phase (tools/dyn_stamps.py) */
     /* (straight to the slot: an array of the six stamps was kept in scratch
      * memory, zeroed by every thread) */
@@ -1623,12 +1644,13 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         f = (int)(q - (uint32_t)s * (uint32_t)ld_fr);
     }
     const size_t nb = (size_t)s * ld_fr + f;
+    if (POS) dyn_frame_geom(gp, nb);
     constexpr bool general = GEN;
     constexpr int SR = DYN_STATIC_ROWS;
     /* the workgroup's slot, a uniform pointer (thread 0 writes: as thread
      * 0's own value it was a VGPR pair held to the kernel's end) */
     uint64_t *stp = nullptr;
-    if (DBG && stamps) stp = stamps + (((size_t)s * gridDim.y + f) * g.ngroups + (max(1, (g.y0 + SR - 1) / SR) + r)) * 8;
+    if (DBG && stamps) stp = stamps + (((size_t)s * gridDim.y + f) * g.ld_groups + (max(1, (g.y0 + SR - 1) / SR) + r)) * 8;
     if (stp && t == 0) stp[0] = t_entry;
     const Rect R{g.x0, g.y0, g.w, g.h};
     const int w = R.w, ndt = R.w * R.h, row = R.y0 + r, npc = NPC * w, ntask = 24 * w;
@@ -2255,7 +2277,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     uint32_t *const rowstage = row_arg(K5, rowstage), *const gbits = row_arg(K5, gbits);
     const uint32_t rs_static_words = row_arg(K5, g.rs_static_words), rs_row_words = row_arg(K5, g.rs_row_words);
     const uint64_t rs_frame_words = row_arg(K5, g.rs_frame_words);
-    if (t == 0) gbits[nb * (size_t)row_arg(K5, g.ngroups) + gi] = bits;
+    if (t == 0) gbits[nb * (size_t)row_arg(K5, g.ld_groups) + gi] = bits;
 
     /* ---- 5: bits -> the row's own row-stage words ------------------------ */
     const bool wwin = row_wide_win(w);
@@ -2514,7 +2536,7 @@ __device__ inline void rs_table(const uint32_t *gbits, size_t nb, const DynGeom 
         const bool row = gi >= nA && gi < nA + g.h;
         uint32_t w = (uint32_t)rs_group_words(g, nA, gi), c = (uint32_t)rs_runs_words(g, nA, gi);
         /* both loads in flight together */
-        const uint32_t b = in ? gbits[nb * (size_t)ng + gi] : 0u;
+        const uint32_t b = in ? gbits[nb * (size_t)g.ld_groups + gi] : 0u;
         uint32_t m = in && (row || cnt) ? fr[c] : 0u;
         const uint32_t incl = wave_incl_sum(b, t);
         if (in) {
@@ -3182,14 +3204,15 @@ __global__ __launch_bounds__(NT) EPF_ATTR void k_dyn_epfix(DevStream *__restrict
 {
     __shared__ __attribute__((aligned(16))) uint32_t lst[LCAP];   /* the position bitmap / list */
     extern __shared__ uint32_t gdyn[];                  /* the group tables (gtab_bytes); cbase: runs before group g */
-    const GTab GT = gtab_of(gdyn, g.ngroups);
-    uint32_t *goff = GT.goff, *gb = GT.gb, *gw = GT.gw, *cw = GT.cw, *cbase = GT.cbase;
     __shared__ uint32_t cnt[4], ws[NT / 64];
     const int f = blockIdx.x, s = blockIdx.y, t = threadIdx.x;
     if (f >= nframes) return;
     const size_t nb = (size_t)s * ld_fr + f;
     DynFrame *DF = dfr + nb;
     if (DF->nal < 0) return;
+    dyn_frame_geom(g, nb);                              /* the frame's own nA and group count (<= ld_groups: the LDS) */
+    const GTab GT = gtab_of(gdyn, g.ngroups);
+    uint32_t *goff = GT.goff, *gb = GT.gb, *gw = GT.gw, *cw = GT.cw, *cbase = GT.cbase;
     const EpfLds E{goff, gb, gw, cw, cbase, lst, cnt, ws};
     ep_fix<NT, LCAP>(st, DF, nb, s, g, rowstage, gbits, eps, E, t, stamps ? stamps + ((size_t)s * nframes + f) * 8 : nullptr);
 }
@@ -3356,9 +3379,10 @@ __global__ __launch_bounds__(DT) void k_dyn_emit_gather(const DevStream *__restr
     __shared__ alignas(16) uint32_t raw[EPLIST_MAX];
     __shared__ uint32_t sp[EPLIST_MAX];
     extern __shared__ uint32_t gdyn[];                  /* RS: the group tables (gtab_bytes) */
+    const int s = blockIdx.y, f = dyn_frame_of(blockIdx.x, s), t = threadIdx.x;
+    if (RS) dyn_frame_geom(g, (size_t)s * ld_fr + f);   /* the frame's own nA and group count */
     const GTab GT = gtab_of(gdyn, RS ? g.ngroups : 0);
     uint32_t *goff = GT.goff, *gb = GT.gb, *gw = GT.gw;
-    const int s = blockIdx.y, f = dyn_frame_of(blockIdx.x, s), t = threadIdx.x;
     /* debug: realtime at entry / after the sort / at exit, EP count, HW_ID */
     uint64_t *stp = stamps && t == 0 && blockIdx.z == 0 ? stamps + ((size_t)s * gridDim.x + f) * 8 : nullptr;
     if (stp) stp[0] = __builtin_amdgcn_s_memrealtime();
@@ -3610,9 +3634,10 @@ __global__ __launch_bounds__(DT) __attribute__((amdgpu_waves_per_eu(8))) void k_
     __shared__ alignas(16) uint32_t raw[EPLIST_MAX];
     __shared__ uint32_t sp[EPLIST_MAX + 1];
     extern __shared__ uint32_t gdyn[];                  /* the group tables (gtab_bytes) */
+    const int s = blockIdx.y, f = dyn_frame_of(blockIdx.x, s), t = threadIdx.x;
+    dyn_frame_geom(g, (size_t)s * ld_fr + f);           /* the frame's own nA and group count */
     const GTab GT = gtab_of(gdyn, g.ngroups);
     uint32_t *goff = GT.goff, *gb = GT.gb, *gw = GT.gw;
-    const int s = blockIdx.y, f = dyn_frame_of(blockIdx.x, s), t = threadIdx.x;
     const DynFrame df = dfr[(size_t)s * ld_fr + f];
     const int j = df.nal;
     if (j < 0 || j >= st[s].nnal || (df.err & ~(DF_EPSLOW | DF_FIXED))) return;   /* nnal = 0: nothing committed */
@@ -3913,11 +3938,12 @@ __device__ inline uint32_t mix32(uint32_t x)
     return x;
 }
 
-__global__ __launch_bounds__(256) void k_dyn_synth(uint8_t *__restrict__ src, DynGeom g,
+__global__ __launch_bounds__(256) void k_dyn_synth(uint8_t *__restrict__ src, DynGeom g, int ld_fr,
                                                    int stream_base, int t0)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     const int f = blockIdx.y, s = blockIdx.z;
+    dyn_frame_geom(g, (size_t)s * ld_fr + f);           /* the pattern is a function of picture coordinates */
     const uint32_t npx = 384u * (uint32_t)g.w * (uint32_t)g.h;
     if (i >= npx) return;
     const uint32_t tt = (uint32_t)(t0 + f);
@@ -3988,8 +4014,12 @@ int dyn_launch_code(hipStream_t hs, int nframes, int S, DevStream *st, const Nal
     if (hipGetLastError() != hipSuccess) return -1;
     /* the debug instantiations only with the stamps or the tests' NOPUBLISH hook on */
     const bool dbg = stamps || (g->debug & SCROLL_DEBUG_DYN_NOPUBLISH);
-    void (*const krow)(RowArgs) = dbg ? &k_dyn_row<false, true> : &k_dyn_row<false, false>;
-    void (*const kgen)(RowArgs) = dbg ? &k_dyn_row<true, true> : &k_dyn_row<true, false>;
+    /* ... and the ones that take each frame's origin from the position table only when there is one */
+    const bool pos = g->dpos != nullptr;
+    void (*const krow)(RowArgs) = pos ? (dbg ? &k_dyn_row<false, true, true> : &k_dyn_row<false, false, true>)
+                                      : (dbg ? &k_dyn_row<false, true, false> : &k_dyn_row<false, false, false>);
+    void (*const kgen)(RowArgs) = pos ? (dbg ? &k_dyn_row<true, true, true> : &k_dyn_row<true, false, true>)
+                                      : (dbg ? &k_dyn_row<true, true, false> : &k_dyn_row<true, false, false>);
     if (row_lds_bytes(g->w) > 65536) {
         /* wide rects (a whole 1280- or 4096-px row): dynamic LDS past the
          * 64 KB default, up to the CU's 160 KB (set_dyn_rect's bound) */
@@ -4046,7 +4076,7 @@ int dyn_launch_static(hipStream_t hs, int nframes, int S, DevStream *st, const N
                       const PlanPending *pend, DynFrame *dfr, int ld_fr, const DynGeom *g, const DynScratch *x)
 {
     if (nframes <= 0 || S <= 0) return 0;
-    hipLaunchKernelGGL(k_dyn_static, dim3(g->ngroups - g->h, nframes, S), dim3(GW), 0, hs, st, nal, ld_nal,
+    hipLaunchKernelGGL(k_dyn_static, dim3(g->ld_groups - g->h, nframes, S), dim3(GW), 0, hs, st, nal, ld_nal,
                        pend, dfr, ld_fr, *g, x->rowstage, x->gbits);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -4062,10 +4092,10 @@ int dyn_launch_pack(hipStream_t hs, int nframes, int S, DevStream *st, const Nal
         return -1;
     }
     if (g->ep_cap >= (uint32_t)EPF_BIG_LIST)
-        hipLaunchKernelGGL((k_dyn_epfix<EPF_T, EPF_BIG_LIST>), dim3(nframes, S), dim3(EPF_T), gtab_bytes(g->ngroups, true),
+        hipLaunchKernelGGL((k_dyn_epfix<EPF_T, EPF_BIG_LIST>), dim3(nframes, S), dim3(EPF_T), gtab_bytes(g->ld_groups, true),
                            hs, st, dfr, ld_fr, nframes, *g, x->rowstage, x->gbits, eps, stamps);
     else
-        hipLaunchKernelGGL((k_dyn_epfix<EPF_T, EPF_LIST>), dim3(nframes, S), dim3(EPF_T), gtab_bytes(g->ngroups, true),
+        hipLaunchKernelGGL((k_dyn_epfix<EPF_T, EPF_LIST>), dim3(nframes, S), dim3(EPF_T), gtab_bytes(g->ld_groups, true),
                            hs, st, dfr, ld_fr, nframes, *g, x->rowstage, x->gbits, eps, stamps);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -4083,7 +4113,7 @@ int dyn_launch_emit(hipStream_t hs, int nframes, int S, const DevStream *st, con
     const bool big = (int64_t)g->w * g->h > 1024;
     const uint32_t *rs = x ? x->rowstage : nullptr, *gbits = x ? x->gbits : nullptr;
     const dim3 grid(nframes, S, GATHER_Z);
-    const size_t gl = x ? gtab_bytes(g->ngroups, false) : 0;     /* the group tables (RS) */
+    const size_t gl = x ? gtab_bytes(g->ld_groups, false) : 0;     /* the group tables (RS) */
     if (x && !(g->debug & SCROLL_DEBUG_DYN_GATHER1))
         hipLaunchKernelGGL(k_dyn_gather, dim3(nframes, S, gather_z(*g, (int64_t)nframes * S)), dim3(DT), gl, hs, st, nal, ld_nal, dfr,
                            ld_fr, *g, stage, rs, gbits, arena, ld_arena, stamps);
@@ -4102,22 +4132,30 @@ int dyn_launch_emit(hipStream_t hs, int nframes, int S, const DevStream *st, con
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int dyn_launch_synth(hipStream_t hs, int nframes, int S, uint8_t *src, const DynGeom *g,
+int dyn_launch_synth(hipStream_t hs, int nframes, int S, uint8_t *src, const DynGeom *g, int ld_fr,
                      int stream_base, int t0)
 {
     if (nframes <= 0 || S <= 0) return 0;
     const uint32_t npx = 384u * (uint32_t)g->w * (uint32_t)g->h;
     hipLaunchKernelGGL(k_dyn_synth, dim3((npx + 255) / 256, nframes, S), dim3(256), 0, hs, src, *g,
-                       stream_base, t0);
+                       ld_fr, stream_base, t0);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-void dyn_rowstage_geom(DynGeom *g, int mbw, int mbh)
+void dyn_rowstage_geom(DynGeom *g, int mbw, int mbh, int moving)
 {
     const int SR = DYN_STATIC_ROWS;
     const int above = g->y0 < SR ? g->y0 : SR, below0 = mbh - g->y0 - g->h;
     const int below = below0 < SR ? below0 : SR;
-    const int maxrows = above > below ? above : below;
+    int maxrows = above > below ? above : below;
+    g->ngroups = dyn_groups_at(g->y0, g->h, mbh);
+    g->ld_groups = g->ngroups;
+    if (moving) {
+        /* every legal y0: a static group of as many rows as the picture
+         * leaves beside the rect, and the placement with the most groups */
+        maxrows = mbh - g->h < SR ? mbh - g->h : SR;
+        g->ld_groups = dyn_groups_max(g->h, mbh);
+    }
     auto words = [](uint64_t bits) { return (uint32_t)((((bits + 31) / 32) + 63) & ~(uint64_t)63); };
     /* + the group's EP-candidate record (EPC_ROW / EPC_STATIC words) at the slot end */
     g->rs_static_words = words((uint64_t)HDR_MAX + (uint64_t)maxrows * mbw * (HEAD_MAX + 1) + 64) + EPC_STATIC;
@@ -4127,7 +4165,7 @@ void dyn_rowstage_geom(DynGeom *g, int mbw, int mbh)
     g->rs_spill_words = words((uint64_t)mbw * (HEAD_MAX + 1) + (uint64_t)g->w * MB_BITS_MAX + 64) + EPC_ROW;
     g->rs_row_words = words((uint64_t)mbw * (HEAD_MAX + 1) + (uint64_t)g->w * SCROLL_DYN_ROW_KBITS + 64) + EPC_ROW;
     if (g->rs_row_words > g->rs_spill_words) g->rs_row_words = g->rs_spill_words;
-    g->rs_frame_words = (uint64_t)(g->ngroups - g->h) * g->rs_static_words + (uint64_t)g->h * g->rs_row_words;
+    g->rs_frame_words = (uint64_t)(g->ld_groups - g->h) * g->rs_static_words + (uint64_t)g->h * g->rs_row_words;
 }
 
 /* EP positions kept per frame by the rows' path (the list buffer's stride / 4) */
@@ -4155,7 +4193,7 @@ extern "C" int scroll_debug_row_occupancy(int w, int mbw, int extra_lds)
     int n = -1;
     (void)mbw;                              /* (round 4's LDS grew with the picture width) */
     const size_t lds = (size_t)((long)row_lds_bytes(w) + extra_lds);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(&k_dyn_row<false, false>),
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(&k_dyn_row<false, false, false>),
                                                      row_threads(w), lds) != hipSuccess)
         return -1;
     return n;

@@ -118,7 +118,15 @@ typedef struct {
     uint32_t gen_cap;               /* general-path record slots (NALs)           */
     uint32_t rs_frames;             /* frame regions before the spill slots (S F)  */
     uint32_t ep_cap;                /* EP positions kept per frame (the dyn path's list; 4 ep_cap bytes a frame) */
+    int32_t ld_groups;              /* row groups a frame's region, its gbits row and the static grid are sized
+                                     * for: ngroups, or with moving rects the most of any legal y0 */
+    /* scroll_batch_set_dyn_rect_moving: the per-frame origins, [s ld_fr + f] =
+     * x0 | y0 << 16 (DYN_POS_NONE: the frame has no rect, and no dynamic NAL);
+     * NULL: every frame at x0, y0.  A kernel that codes frame (s, f) replaces
+     * x0, y0 and ngroups of its copy by the frame's (dyn_frame_geom) */
+    const uint32_t *dpos;
 } DynGeom;
+#define DYN_POS_NONE 0xffffffffu
 
 /* hints of one composed frame: rects [first, first + n) of the batch's rect
  * pool, SCROLL_HINT_* mode.  8 bytes. */

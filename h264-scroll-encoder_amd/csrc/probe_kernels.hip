@@ -29,6 +29,7 @@
 #include "recon_pred.h"
 #include "probe_device.h"
 #include "dyn_engine.h"
+#include "dyn_pos.h"
 #include "probe_engine.h"
 
 using namespace scroll;
@@ -116,6 +117,7 @@ __global__ __launch_bounds__(PB_T) void k_dyn_probe(const DevStream *__restrict_
     const int s = (int)(nb / (size_t)ld_fr), f = (int)(nb - (size_t)s * ld_fr);
     const DynFrame df = dfr[nb];
     if (df.nal < 0) return;                              /* no dynamic NAL in this frame */
+    dyn_frame_geom(g, nb);                               /* RowPred's origin, avl / avt: the frame's own */
     const bool above = r > 0;                            /* the row above is a rect row */
     if (t < 64) {
         const int i = t & 31, rr = t < 32 ? r : (above ? r - 1 : r);

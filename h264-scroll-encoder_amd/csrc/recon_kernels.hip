@@ -25,6 +25,7 @@
 #include "recon_device.h"
 #include "recon_block.h"
 #include "dyn_engine.h"
+#include "dyn_pos.h"
 #include "nal_ctx.h"
 #include "recon_engine.h"
 #include "recon_pred.h"
@@ -65,6 +66,7 @@ __global__ __launch_bounds__(RC_T) void k_dyn_recon(const DevStream *__restrict_
     const int s = (int)(nb / (size_t)ld_fr), f = (int)(nb - (size_t)s * ld_fr);
     const DynFrame df = dfr[nb];
     if (df.nal < 0) return;                              /* no dynamic NAL in this frame */
+    dyn_frame_geom(g, nb);                               /* RowPred's origin: the frame's own */
     if (t < 32)
         L.rt[t] = rows[nb * (size_t)(32 * g.h) +
                        (t < 16 ? 16 * r + t : 16 * g.h + (t < 24 ? 8 * r + t - 16 : 8 * g.h + 8 * r + t - 24))];

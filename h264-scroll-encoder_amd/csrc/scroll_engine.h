@@ -21,11 +21,13 @@ constexpr int PLAN_DYN = 1 << 11;     /* scroll NALs carry the dynamic rect     
 /* k_plan, one workgroup per stream.  The plain call stops at ld_fr; the
  * state pass (PLAN_STATE) names in ctr_zero the dynamic rect's counters to
  * zero; the size pass (PLAN_SIZE) names them in pool_ctr, with the pools'
- * caps, to fail the compose that ran out of one */
+ * caps, to fail the compose that ran out of one.  dpos (both passes of a
+ * compose with moving rects, DynGeom.dpos): the frames whose entry is
+ * DYN_POS_NONE get no dynamic NAL (DynFrame.nal = -1, their scroll NAL plain) */
 void scroll_launch_plan(hipStream_t hs, int S, DevStream *st, const int32_t *offs, int ld_off, NalDesc *nal,
                         int ld_nal, int nframes, int mode, int flags, PlanPending *pend, DynFrame *dfr, int ld_fr,
                         const uint32_t *pool_ctr = nullptr, uint32_t spill_cap = 0, uint32_t gen_cap = 0,
-                        uint32_t *ctr_zero = nullptr);
+                        uint32_t *ctr_zero = nullptr, const uint32_t *dpos = nullptr);
 /* k_emit over up to nal_max NALs per stream; nothing when that is none */
 void scroll_launch_emit(hipStream_t hs, int S, int nal_max, const DevStream *st, const NalDesc *nal, int ld_nal,
                         uint8_t *arena, uint64_t ld_arena, int flags, uint64_t *dbg);

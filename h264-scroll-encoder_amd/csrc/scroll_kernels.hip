@@ -103,7 +103,8 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan(DevStream *__restrict__ s
                                                        DynFrame *__restrict__ dfr, int ld_fr,
                                                        const uint32_t *__restrict__ pool_ctr = nullptr,
                                                        uint32_t spill_cap = 0, uint32_t gen_cap = 0,
-                                                       uint32_t *__restrict__ ctr_zero = nullptr)
+                                                       uint32_t *__restrict__ ctr_zero = nullptr,
+                                                       const uint32_t *__restrict__ dpos = nullptr)
 {
     const int s = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -223,7 +224,10 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan(DevStream *__restrict__ s
                     d.kind = 0; d.off = off; d.frame_num = fn0 + first + has_wp;
                     d.nwp = (uint8_t)my_n; d.frame = (uint32_t)i;
                     N[first + has_wp] = d;
-                    if (flags & PLAN_DYN) dfr[(size_t)s * ld_fr + i].nal = first + has_wp;
+                    /* dpos (the plain rect's per-frame origins): a frame without a rect has no dynamic NAL */
+                    if (flags & PLAN_DYN)
+                        dfr[(size_t)s * ld_fr + i].nal =
+                            dpos && dpos[(size_t)s * ld_fr + i] == DYN_POS_NONE ? -1 : first + has_wp;
                 }
                 nalc += __popcll(vmask) + __popcll(wmask);
             } else {   /* experiment: waypoint NAL replaces the scroll NAL */
@@ -233,7 +237,9 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan(DevStream *__restrict__ s
                     d.kind = has_wp ? 1 : 0; d.off = off; d.frame_num = fn0 + idx;
                     d.nwp = (uint8_t)(has_wp ? wp_nb : my_n); d.frame = (uint32_t)i;
                     N[idx] = d;
-                    if (flags & PLAN_DYN) dfr[(size_t)s * ld_fr + i].nal = has_wp ? -1 : idx;
+                    if (flags & PLAN_DYN)
+                        dfr[(size_t)s * ld_fr + i].nal =
+                            has_wp || (dpos && dpos[(size_t)s * ld_fr + i] == DYN_POS_NONE) ? -1 : idx;
                 }
                 nalc += __popcll(vmask);
             }
@@ -282,7 +288,8 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_plan(DevStream *__restrict__ s
             NalDesc d = N[j];
             NalCtx c = make_ctx(s_cfg, s_wo, s_wl, s_wv, d);
             uint32_t fsz = 0;
-            const bool dyn = (flags & PLAN_DYN) && d.kind == 0;
+            /* (DynFrame.nal < 0 on a scroll NAL: only with dpos, a frame without a rect -- k_emit's) */
+            const bool dyn = (flags & PLAN_DYN) && d.kind == 0 && (!dpos || dfr[(size_t)s * ld_fr + d.frame].nal >= 0);
             bool fast = !dyn && !(flags & SCROLL_DEBUG_FORCE_SERIAL) && build_nal<false>(c, nullptr, &fsz);
             if (dyn) {
                 const DynFrame df = dfr[(size_t)s * ld_fr + d.frame];
@@ -870,10 +877,11 @@ __global__ __launch_bounds__(256) void k_out_copy(const DevStream *__restrict__ 
 /* ---------------------------------------------------------------------- */
 void scroll_launch_plan(hipStream_t hs, int S, DevStream *st, const int32_t *offs, int ld_off, NalDesc *nal,
                         int ld_nal, int nframes, int mode, int flags, PlanPending *pend, DynFrame *dfr, int ld_fr,
-                        const uint32_t *pool_ctr, uint32_t spill_cap, uint32_t gen_cap, uint32_t *ctr_zero)
+                        const uint32_t *pool_ctr, uint32_t spill_cap, uint32_t gen_cap, uint32_t *ctr_zero,
+                        const uint32_t *dpos)
 {
     hipLaunchKernelGGL(k_plan, dim3(S), dim3(PLAN_THREADS), 0, hs, st, offs, ld_off, nal, ld_nal, nframes, mode,
-                       flags, pend, dfr, ld_fr, pool_ctr, spill_cap, gen_cap, ctr_zero);
+                       flags, pend, dfr, ld_fr, pool_ctr, spill_cap, gen_cap, ctr_zero, dpos);
 }
 
 static int emit_gx(int nal_max)

@@ -211,6 +211,7 @@ def _load():
                                                       ctypes.c_int]),
         "scroll_batch_set_dyn_source": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_int]),
         "scroll_batch_set_dyn_rect_at": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
+        "scroll_batch_set_dyn_rect_moving": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
         "scroll_batch_set_fallback": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
         "scroll_batch_fallback_frame": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                        ctypes.POINTER(ctypes.c_int)]),
@@ -708,8 +709,15 @@ class Batch:
     def set_dyn_rect_at(self, s, f, x0, y0):
         """Frame f of stream s puts the dynamic rect at MB (x0, y0); x0 = -1:
         no rect in that frame.  Positions other than set_dyn_rect's need UI
-        hints (set_hints) at compose time."""
+        hints (set_hints) at compose time, or set_dyn_rect_moving."""
         self._chk(lib.scroll_batch_set_dyn_rect_at(self.h, s, f, x0, y0), "set_dyn_rect_at")
+
+    def set_dyn_rect_moving(self, on=True):
+        """the plain rect placed per stream and per frame on the fast path: a
+        compose without hints honours set_dyn_rect_at's positions (entry f:
+        frame f of every compose; x0 = -1: a plain scroll NAL).  Needs a
+        dynamic rect; set_dyn_rect drops the flag."""
+        self._chk(lib.scroll_batch_set_dyn_rect_moving(self.h, 1 if on else 0), "set_dyn_rect_moving")
 
     def set_fallback(self, on=True):
         """the conventional-encode fallback (scroll_batch_set_fallback): frames

@@ -217,14 +217,36 @@ int scroll_batch_set_dyn_source(ScrollBatch *b, const uint8_t *src, int nframes)
  * motion -- and the rect may sit anywhere in each frame:
  *   scroll_batch_set_dyn_rect_at(b, s, f, x0, y0)   frame f of stream s puts
  *       the rect's w x h MBs at (x0, y0); x0 = -1: no rect in that frame.
- *       Positions other than set_dyn_rect's need hints at compose time
- *       (SCROLL_ERR_CONFIG otherwise); clear_hints resets them.
+ *       Positions other than set_dyn_rect's need hints at compose time, or
+ *       scroll_batch_set_dyn_rect_moving below (SCROLL_ERR_CONFIG otherwise);
+ *       set_dyn_rect and clear_hints reset them.
  * Each rect MB's residual bits get a region of slot_bytes / (w h) bytes
  * (64 to 2048; slot_bytes 0: 512, which saturated +-255 residuals stay well
  * inside); an MB that outgrows it fails the compose with SCROLL_ERR_OVERFLOW.
  * Bit-exact definition: oracle/splice_oracle.h or_hint_dyn_scroll_nal.
  * Not combinable with spliced slices (one rect per frame). */
 int scroll_batch_set_dyn_rect_at(ScrollBatch *b, int s, int f, int x0, int y0);
+/* The plain rect (no hints) placed per stream and per frame, on the fast
+ * path (k_dyn_rows / k_dyn_row / k_dyn_static / k_dyn_epfix / k_dyn_gather):
+ *   scroll_batch_set_dyn_rect_moving(b, 1)   a compose without hints honours
+ *       set_dyn_rect_at's positions: entry [s max_frames + f] applies to
+ *       frame f of every following compose.  Frame f with its rect at (x, y)
+ *       is, byte for byte, NAL f of the same compose with the batch rect at
+ *       (x, y) -- prediction is from the static pictures only; a frame
+ *       without a rect (x0 = -1) carries the plain scroll NAL the batch
+ *       writes with the rect off, has no dynamic NAL (scroll_batch_dyn_frame_info,
+ *       _dyn_recon, _dyn_sse, the probe's results and the pick return 1 /
+ *       leave it alone, as for a frame the experiment mode replaced) and keeps
+ *       its source bytes.  The per-frame QP table, the reconstruction, the
+ *       probe, the pick, dyn_source_synth and dyn_source_from_surfaces follow
+ *       the positions.  Needs a dynamic rect (SCROLL_ERR_CONFIG without one);
+ *       sizes the row stage once for every legal position, so no later
+ *       set_dyn_rect_at allocates; scroll_batch_set_dyn_rect drops the flag
+ *       with the rect.  With hints set the hinted path runs as it always has
+ *       and the flag changes nothing there; scroll_batch_set_fallback stays
+ *       hints-only.  Off (the default): nothing changes -- a moved position
+ *       without hints is refused at compose time. */
+int scroll_batch_set_dyn_rect_moving(ScrollBatch *b, int on);
 /* The conventional-encode fallback (docs/MASTER_DESIGN.md:220: "if hints
  * missing/inconsistent -> full conventional encode"), opt-in:
  *   scroll_batch_set_fallback(b, 1)   with UI hints and a dynamic rect that
