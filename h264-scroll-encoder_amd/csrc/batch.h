@@ -7,6 +7,7 @@
  *   batch_hint.hip    UI hints, the rect under hints, the splice
  *   batch_ingest.hip  ingest, I_PCM files, reference updates
  *   batch_surface.hip pixels from RGBA / BGRA surfaces: the rect's source, I420 pictures, device references
+ *   batch_damage.hip  the rect located from the surfaces: damage map, placement, the positions' device ownership
  *   batch_dropin.hip  the synchronous drop-in helpers of engine.h
  * Nothing here enters the library's dynamic symbol table.
  */
@@ -131,6 +132,22 @@ struct ScrollBatch {
         hipEvent_t ev[2] = {};          /* timing: around the last conversion (created on first use) */
         int timed = 0;
     } sf;
+    /* the rect located from the surfaces (scroll_batch_dyn_locate,
+     * batch_damage.hip, damage_kernels.hip): a dry plan, the prediction rows
+     * of whole pictures, the map and the records; nothing here exists before
+     * the first locate, everything goes with the rect */
+    struct Locate {
+        NalDesc *nal = nullptr;
+        DynFrame *dfr = nullptr;
+        PlanPending *pend = nullptr;
+        uint32_t *rows = nullptr;       /* [max_streams * max_frames][ph] */
+        uint32_t *map = nullptr;        /* [max_streams * max_frames][mbh][mbw] */
+        ScrollDynDamage *res = nullptr; /* [max_streams * max_frames] */
+        int nframes = -1, nstreams = 0; /* the last locate; nframes -1: none */
+        hipEvent_t fin = nullptr;       /* recorded after the last locate's launches */
+        hipEvent_t ev[4] = {};          /* timing: the call's start, around k_dyn_damage, its end (created on first use) */
+        int timed = 0;
+    } lc;
     /* UI hints: staged like the dynamic rect (shares
      * d_dfr, d_stage and geo.slot_bytes; the two are exclusive) */
     int hint_on = 0;
@@ -168,6 +185,10 @@ struct ScrollBatch {
     std::vector<uint32_t> h_dpos;      /* what was uploaded there (the copy's source until the stream has run it) */
     int dpos_stale = 1;                /* h_dyn_pos changed since the upload */
     int dpos_any = 0;                  /* as of the upload: some entry differs */
+    /* a locate with apply wrote entries of d_dpos (batch_damage.hip): the
+     * device's table is the truth and h_dyn_pos / dyn_pos_custom are behind
+     * until dyn_pos_refresh reads it back; never set together with dpos_stale */
+    int dpos_dev = 0;
     hipStream_t dpos_hs = nullptr;     /* the stream that upload ran on ... */
     hipEvent_t dpos_ev = nullptr;      /* ... and its end: other streams wait for it, the next packing too */
     int dyn_qp = 26;                   /* the rect's QP (scroll_batch_set_dyn_qp)          */
@@ -279,6 +300,15 @@ int ipcm_async_check(ScrollBatch *b);
 /* the per-frame position table goes with the rect (all = false); the timing
  * events with the batch (all = true) */
 void surface_release(ScrollBatch *b, bool all);
+/* what every surface call asks of the surfaces: w pixels of every row lie inside the pitch */
+int surf_args(const char *who, const ScrollSurfaces *surf, uint64_t w, bool streams);
+
+/* ---- batch_damage.hip ---- */
+void locate_release(ScrollBatch *b);
+/* before host code reads or merges into h_dyn_pos / dyn_pos_custom: when a
+ * locate has placed frames on the device, wait for it and read the table
+ * back (synchronising); otherwise nothing */
+int dyn_pos_refresh(ScrollBatch *b);
 
 }  // namespace batch
 }  // namespace scroll

@@ -541,6 +541,7 @@ void scroll_batch_destroy(ScrollBatch *b)
     for (hipEvent_t e : b->rc_ev)
         if (e) (void)hipEventDestroy(e);
     probe_release(b);
+    locate_release(b);
     (void)hipFree(b->dx.qpf);
     rate_release(b);
     surface_release(b, true);
@@ -697,6 +698,12 @@ int scroll_batch_compose_ex(ScrollBatch *b, int nframes, void *hip_stream, int f
     }
     HIPCHK(hipSetDevice(b->device));
     const bool combined = b->hint_on && b->dyn_on;
+    /* located positions (scroll_batch_dyn_locate) that anything but the plain
+     * moving rect's kernels is about to read: the host's copy first */
+    if (b->dpos_dev && (b->hint_on || !b->dyn_moving)) {
+        int rc = dyn_pos_refresh(b);
+        if (rc) return rc;
+    }
     if (b->dyn_pos_custom && !b->hint_on && !b->dyn_moving) {
         set_err("scroll_batch_compose: per-frame dynamic rect positions need UI hints "
                 "(scroll_batch_set_hints)");

@@ -48,6 +48,7 @@ void probe_release(ScrollBatch *b)
 void dyn_release(ScrollBatch *b)
 {
     probe_release(b);
+    locate_release(b);                 /* the locate's buffers, and the device's ownership of the positions */
     if (!b->hint_on) {                 /* else they are the hint path's */
         (void)hipFree(b->d_dfr);
         (void)hipFree(b->d_stage);
@@ -319,6 +320,8 @@ int dyn_pos_table(ScrollBatch *b, hipStream_t hs, const uint32_t **dpos)
 {
     *dpos = nullptr;
     if (!b->dyn_on || !b->dyn_moving || b->hint_on) return SCROLL_OK;
+    /* (a table a locate has written, dpos_dev, is never stale: it is handed
+     * out below as the device left it, nothing uploaded over it) */
     if (b->dpos_stale) {
         /* the last upload has read its source */
         if (b->dpos_hs) HIPCHK(hipEventSynchronize(b->dpos_ev));
@@ -483,6 +486,8 @@ int scroll_batch_set_dyn_rect_at(ScrollBatch *b, int s, int f, int x0, int y0)
     if (rc) return rc;
     /* with moving rects a probe on a stream of its own may still read the device table */
     if (b->dyn_moving && b->pb.fin) HIPCHK(hipEventSynchronize(b->pb.fin));
+    /* positions a locate placed on the device stay, all but this one */
+    if ((rc = dyn_pos_refresh(b))) return rc;
     const size_t i = (size_t)s * b->max_frames + f;
     b->h_dyn_pos[2 * i] = x0 < 0 ? -1 : x0;
     b->h_dyn_pos[2 * i + 1] = x0 < 0 ? -1 : y0;
@@ -514,6 +519,7 @@ int scroll_batch_set_dyn_rect_moving(ScrollBatch *b, int on)
     HIPCHK(hipSetDevice(b->device));
     if (b->pb.fin) HIPCHK(hipEventSynchronize(b->pb.fin));     /* a probe on another stream */
     if (b->dpos_ev) HIPCHK(hipEventSynchronize(b->dpos_ev));
+    if ((rc = dyn_pos_refresh(b))) return rc;                   /* located positions outlive the table */
     DynGeom g = b->geo;
     dyn_rowstage_geom(&g, b->dyn_pw / 16, b->dyn_ph / 16, on ? 1 : 0);
     const size_t S = (size_t)b->max_streams, F = (size_t)b->max_frames;

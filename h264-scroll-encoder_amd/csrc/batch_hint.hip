@@ -60,6 +60,8 @@ namespace batch {
 /* host hint tables -> d_hf (per frame) + d_pool (all rects) */
 int hint_upload(ScrollBatch *b)
 {
+    int prc = dyn_pos_refresh(b);      /* positions a locate placed before the hints came */
+    if (prc) return prc;
     const size_t n = b->h_hint.size();
     std::vector<HintFrame> hf(n);
     std::vector<ScrollHintRect> pool;
@@ -123,6 +125,8 @@ int hd_upload(ScrollBatch *b)
 {
     const size_t S = (size_t)b->max_streams, F = (size_t)b->max_frames;
     const size_t nmb = (size_t)b->geo.w * b->geo.h;
+    int prc = dyn_pos_refresh(b);      /* positions a locate placed before the hints came */
+    if (prc) return prc;
     std::vector<SpliceFrame> spf(S * F);
     for (size_t i = 0; i < S * F; ++i) {
         SpliceFrame &o = spf[i];
@@ -354,7 +358,9 @@ int scroll_batch_clear_hints(ScrollBatch *b)
             return hip_fail("scroll_batch_clear_hints", e);
         }
         b->geo.slot_bytes = b->dyn_cap;
-        if (b->dyn_pos_custom) {
+        if (b->dyn_pos_custom || b->dpos_dev) {            /* (located positions go too, unread) */
+            if (b->dpos_dev) HIPCHK(hipEventSynchronize(b->dpos_ev));
+            b->dpos_dev = 0;
             for (size_t i = 0; i < S * F; ++i) {
                 b->h_dyn_pos[2 * i] = b->geo.x0;
                 b->h_dyn_pos[2 * i + 1] = b->geo.y0;

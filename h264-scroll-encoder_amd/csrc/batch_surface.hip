@@ -38,11 +38,8 @@ void surface_release(ScrollBatch *b, bool all)
     sf.timed = 0;
 }
 
-}  // namespace batch
-}  // namespace scroll
-
-/* what both conversions ask of the surfaces: w pixels of every row lie inside the pitch */
-static int surf_args(const char *who, const ScrollSurfaces *surf, uint64_t w, bool streams)
+/* what every surface call asks of the surfaces: w pixels of every row lie inside the pitch */
+int surf_args(const char *who, const ScrollSurfaces *surf, uint64_t w, bool streams)
 {
     if (!surf || !surf->base) {
         set_err("%s: no surfaces", who);
@@ -66,6 +63,9 @@ static int surf_args(const char *who, const ScrollSurfaces *surf, uint64_t w, bo
     }
     return SCROLL_OK;
 }
+
+}  // namespace batch
+}  // namespace scroll
 
 /* the launches of one conversion, between the timing events when timing is on */
 static int surf_run(ScrollBatch *b, hipStream_t hs, const CscJob &job, const char *who)
@@ -133,7 +133,19 @@ int scroll_batch_dyn_source_from_surfaces(ScrollBatch *b, int nframes, const Scr
         set_err("%s: more than 2^35 pixels in one call: convert fewer frames at a time", who);
         return SCROLL_ERR_ARG;
     }
-    if (b->dyn_pos_custom) {
+    /* positions a locate placed on the device (scroll_batch_dyn_locate with
+     * apply): the plain moving rect reads them in place, no host step; any
+     * other configuration first brings the host's copy up to date */
+    const bool located = b->dpos_dev && b->dyn_moving && !b->hint_on && !b->fallback;
+    if (b->dpos_dev && !located) {
+        const int pr = dyn_pos_refresh(b);
+        if (pr) return pr;
+    }
+    if (located) {
+        if (hs != b->dpos_hs) HIPCHK(hipStreamWaitEvent(hs, b->dpos_ev, 0));   /* located on another stream */
+        job.dpos = b->d_dpos;
+        job.dpos_ld = (uint32_t)b->max_frames;
+    } else if (b->dyn_pos_custom) {
         /* the origins of this call's frames, compact; the table is the
          * batch's, so the previous call's kernel must have read it.  With
          * the fallback on, a frame without the rect keeps a dormant

@@ -22,6 +22,10 @@ typedef struct {
     uint8_t *dst;
     uint64_t dst_fr, dst_ld;
     const int32_t *pos;
+    /* or, in place of pos, the batch's packed position table (DynGeom.dpos's
+     * form: x0 | y0 << 16, DYN_POS_NONE: skipped), item (s, f) at dpos[s dpos_ld + f] */
+    const uint32_t *dpos;
+    uint32_t dpos_ld;
     int32_t x0, y0;
     uint32_t w, h;
     uint32_t S, nframes;

@@ -65,7 +65,11 @@ __global__ __launch_bounds__(CSC_T) void k_csc(CscArgs a)
         const uint32_t rp = divmod(r, a.cw, a.m_cw, &cg);
         const uint32_t s = divmod(item, j.nframes, a.m_nf, &f);
         int32_t x0 = j.x0, y0 = j.y0;
-        if (j.pos) {
+        if (j.dpos) {
+            const uint32_t e = j.dpos[(uint64_t)s * j.dpos_ld + f];
+            x0 = e == 0xFFFFFFFFu ? -1 : (int32_t)(e & 0xFFFFu);
+            y0 = (int32_t)(e >> 16);
+        } else if (j.pos) {
             /* (x, y) in one 8-byte load */
             const uint64_t p = reinterpret_cast<const uint64_t *>(j.pos)[(uint64_t)s * j.nframes + f];
             x0 = (int32_t)(uint32_t)p;

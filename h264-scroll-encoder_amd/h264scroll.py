@@ -153,6 +153,22 @@ class ScrollSurfaces(ctypes.Structure):
                 ("full_range", ctypes.c_uint32), ("cropped", ctypes.c_uint32)]
 
 
+SCROLL_DYN_LOC_NONE, SCROLL_DYN_LOC_FIT, SCROLL_DYN_LOC_OVER, SCROLL_DYN_LOC_NOFRAME = 0, 1, 2, 3
+
+
+class ScrollDynDamage(ctypes.Structure):
+    """include/composer_batch.h: one frame's record of scroll_batch_dyn_locate"""
+    _fields_ = [("x0", ctypes.c_int16), ("y0", ctypes.c_int16), ("bx0", ctypes.c_uint16), ("by0", ctypes.c_uint16),
+                ("bx1", ctypes.c_uint16), ("by1", ctypes.c_uint16), ("status", ctypes.c_uint16),
+                ("reserved", ctypes.c_uint16), ("n_mb", ctypes.c_uint32), ("max_sse", ctypes.c_uint32),
+                ("sse_all", ctypes.c_uint64), ("sse_out", ctypes.c_uint64)]
+
+
+class ScrollDynLocate(ctypes.Structure):
+    _fields_ = [("mb_sse", ctypes.c_uint32), ("margin", ctypes.c_uint32), ("apply", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} not built: run `make -C h264-scroll-encoder_amd` "
@@ -299,6 +315,17 @@ def _load():
         "scroll_batch_set_dyn_refs_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                                             ctypes.c_void_p]),
         "scroll_batch_surface_ms": (ctypes.c_float, [ctypes.c_void_p]),
+        "scroll_batch_dyn_locate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, P(ScrollSurfaces),
+                                                   P(ScrollDynLocate), ctypes.c_void_p]),
+        "scroll_batch_dyn_locate_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                          P(ScrollDynDamage)]),
+        "scroll_batch_dyn_locate_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t)]),
+        "scroll_batch_dyn_damage_map": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                       P(ctypes.c_uint32)]),
+        "scroll_batch_dyn_damage_map_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t),
+                                                                 P(ctypes.c_size_t)]),
+        "scroll_batch_dyn_locate_ms": (ctypes.c_float, [ctypes.c_void_p]),
+        "scroll_batch_dyn_locate_kernel_ms": (ctypes.c_float, [ctypes.c_void_p]),
         "composer_batch_write_scroll_frames": (ctypes.c_int, [P(P(Composer)), P(ctypes.c_int),
                                                               ctypes.c_int, ctypes.c_int]),
         "composer_flush": (ctypes.c_int, [P(Composer)]),
@@ -772,6 +799,65 @@ class Batch:
         launches (-1 without)"""
         return lib.scroll_batch_surface_ms(self.h)
 
+    # ---- the rect located from the surfaces ----
+    def dyn_locate(self, ptr, nframes, pitch, frame_stride, stream_stride=0, fmt=SCROLL_SURF_RGBA,
+                   matrix=SCROLL_SURF_BT601, full_range=False, mb_sse=0, margin=0, apply=True, stream=None):
+        """frames 0 .. nframes - 1 of every stream: the per-MB squared luma
+        difference between the whole-picture surfaces (dyn_source_from_surfaces'
+        layout) and the scroll prediction at set_offsets' offsets, and from it
+        each frame's rect position (scroll_batch_dyn_locate): an MB is damaged
+        when its sum exceeds mb_sse, the damaged MBs' box grows by margin MBs.
+        apply: the positions become the frames' (needs set_dyn_rect_moving);
+        dyn_source_from_surfaces, dyn_probe and compose on the same `stream`
+        then follow them without a host step.  Asynchronous on `stream`"""
+        sf = ScrollSurfaces(ptr, pitch, frame_stride, stream_stride, fmt, matrix, 1 if full_range else 0, 0)
+        rule = ScrollDynLocate(int(mb_sse), int(margin), 1 if apply else 0, 0)
+        self._chk(lib.scroll_batch_dyn_locate(self.h, nframes, ctypes.byref(sf), ctypes.byref(rule), stream),
+                  "dyn_locate")
+
+    def dyn_locate_result(self, nframes):
+        """the last dyn_locate's records: a numpy structured array [S][nframes]
+        with ScrollDynDamage's fields (x0 = -1: no rect; status
+        SCROLL_DYN_LOC_*).  Synchronises"""
+        import numpy as np
+        out = np.zeros((self.num_streams, nframes), dtype=_damage_dtype())
+        r = ScrollDynDamage()
+        for s in range(out.shape[0]):
+            for f in range(nframes):
+                self._chk(lib.scroll_batch_dyn_locate_result(self.h, s, f, ctypes.byref(r)), "dyn_locate_result")
+                out[s, f] = tuple(getattr(r, n) for n in out.dtype.names)
+        return out
+
+    def dyn_damage_map(self, nframes):
+        """the last dyn_locate's map: uint32 [S][nframes][mbh][mbw].  Synchronises"""
+        import numpy as np
+        c = self.config(0)
+        mbw, mbh = c.width // 16, c.height // 16
+        out = np.zeros((self.num_streams, nframes, mbh, mbw), dtype=np.uint32)
+        for s in range(out.shape[0]):
+            for f in range(nframes):
+                self._chk(lib.scroll_batch_dyn_damage_map(self.h, s, f,
+                                                          out[s, f].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
+                          "dyn_damage_map")
+        return out
+
+    def dyn_locate_device(self):
+        """(device pointer, stream stride in bytes) of the records, ScrollDynDamage [stream][frame]"""
+        ls = ctypes.c_size_t()
+        p = lib.scroll_batch_dyn_locate_device(self.h, ctypes.byref(ls))
+        return p, ls.value
+
+    def dyn_damage_map_device(self):
+        """(device pointer, stream stride, frame stride in bytes) of the map, uint32 [stream][frame][mbh][mbw]"""
+        ls, lf = ctypes.c_size_t(), ctypes.c_size_t()
+        p = lib.scroll_batch_dyn_damage_map_device(self.h, ctypes.byref(ls), ctypes.byref(lf))
+        return p, ls.value, lf.value
+
+    def dyn_locate_ms(self, kernel=False):
+        """with enable_timing: HIP-event ms of the last dyn_locate's launches
+        (kernel: of k_dyn_damage alone); -1 without"""
+        return (lib.scroll_batch_dyn_locate_kernel_ms if kernel else lib.scroll_batch_dyn_locate_ms)(self.h)
+
     def dyn_source_synth(self, nframes, stream_base=0, t0=0):
         self._chk(lib.scroll_batch_dyn_source_synth(self.h, nframes, stream_base, t0),
                   "dyn_source_synth")
@@ -970,6 +1056,13 @@ class Batch:
 def _probe_dtype():
     import numpy as np
     return np.dtype([("sse", np.uint64, 3), ("bits", np.uint32), ("nonzero", np.uint32), ("valid", np.uint8)])
+
+
+def _damage_dtype():
+    import numpy as np
+    return np.dtype([("x0", np.int16), ("y0", np.int16), ("bx0", np.uint16), ("by0", np.uint16), ("bx1", np.uint16),
+                     ("by1", np.uint16), ("status", np.uint16), ("reserved", np.uint16), ("n_mb", np.uint32),
+                     ("max_sse", np.uint32), ("sse_all", np.uint64), ("sse_out", np.uint64)])
 
 
 def pick_qp(res, qps, max_bits):

@@ -823,6 +823,81 @@ int scroll_batch_surfaces_to_i420(ScrollBatch *b, int n, int w, int h, const Scr
 int scroll_batch_set_dyn_refs_device(ScrollBatch *b, int s, const uint8_t *d_ref_a, const uint8_t *d_ref_b);
 float scroll_batch_surface_ms(ScrollBatch *b);   /* with enable_timing; -1 without */
 
+/* ---- the dynamic rect located from the surfaces (docs/MASTER_DESIGN.md §7.1) ----
+ * Where the rect sits need not come from the renderer: the device holds the
+ * surfaces and the exact luma a decoder shows for a scroll MB without
+ * residual, and compares the two per MB (csrc/damage_device.h):
+ *     D(mx, my) = sum over the MB's 256 pixels of (Ysrc - Ypred)^2
+ * Ysrc: the luma rule above on the surface pixel; Ypred: the luma prediction
+ * of the scroll NAL a compose at scroll_batch_set_offsets' offsets would
+ * write for the frame (full-pel rows of reference picture A / B, waypoints
+ * resolved).  Luma only: a change of colour with unchanged luma is not seen.
+ * Against the prediction: with the loop filter on (an ingested stream) the
+ * decoded picture can differ from it at the seam of the two regions.
+ * An MB is damaged iff D > mb_sse; the damaged MBs' bounding box, grown by
+ * margin MBs (0..4) on each side and clipped to the picture, is where the
+ * w x h rect goes: x0 = min(bx0, mbw - w), y0 = min(by0, mbh - h).
+ *   SCROLL_DYN_LOC_NONE     nothing damaged: no rect (x0 = y0 = -1), box 0
+ *   SCROLL_DYN_LOC_FIT      the box is at most w x h: the rect covers it
+ *   SCROLL_DYN_LOC_OVER     it is larger: the rect covers its top-left part
+ *   SCROLL_DYN_LOC_NOFRAME  the frame has no scroll NAL (experiment mode's
+ *                           waypoint frame): no rect, zero map entries
+ * sse_all: the sum of D over the picture, sse_out: over the MBs outside the
+ * placed rect (sse_all without one) -- the luma squared error of the
+ * displayed frame that the rect cannot mend, in scroll_batch_dyn_sse's units;
+ * max_sse: the largest D.
+ *
+ *   scroll_batch_dyn_locate(b, nframes, &surf, &rule, hip_stream)
+ *       frames 0 .. nframes - 1 of every stream: the map, the records and,
+ *       with rule.apply = 1, the frames' positions (what
+ *       scroll_batch_set_dyn_rect_at would have been called with; entries
+ *       from nframes on keep their values).  A dry state pass (nothing of the
+ *       batch's state changes), then k_dmg_rows, k_dyn_damage, k_dyn_place.
+ *       Asynchronous on hip_stream (0 = the batch's own), which must be the
+ *       stream of the surface conversion, probe and compose that follow: a
+ *       tick is set_offsets -> locate -> dyn_source_from_surfaces (which cuts
+ *       at the located positions) -> [probe -> pick] -> compose, without a
+ *       host synchronisation.  Reading the positions on the host
+ *       (scroll_batch_set_dyn_rect_at merging one entry, hints turned on,
+ *       scroll_batch_set_dyn_rect_moving off) synchronises and reads them back.
+ *       The surfaces are whole pictures: cropped = 1 is SCROLL_ERR_ARG, as
+ *       are the surface checks above, nframes outside 0..max_frames, margin
+ *       > 4 and apply > 1.  SCROLL_ERR_CONFIG without a dynamic rect with
+ *       reference pictures, with UI hints set, and for apply = 1 without
+ *       scroll_batch_set_dyn_rect_moving.  A refused call writes nothing.
+ *       Buffers (records, map, a row table of 4 bytes per picture row and
+ *       frame, the dry pass's plan) are allocated by the first call and go
+ *       with the rect; a batch that never calls it gains no launch,
+ *       allocation or changed byte.
+ *   scroll_batch_dyn_locate_result / _damage_map   one frame's record / its
+ *       mbw * mbh map entries, row by row (synchronising; SCROLL_ERR_CONFIG
+ *       before the first locate, SCROLL_ERR_ARG outside the last one)
+ *   scroll_batch_dyn_locate_device / _damage_map_device   the device arrays,
+ *       [stream][frame] records (stream_stride in bytes) and [stream][frame]
+ *       [mbh][mbw] uint32 (strides in bytes); NULL before the first locate
+ *   scroll_batch_dyn_locate_ms   with scroll_batch_enable_timing: HIP-event
+ *       ms of the last locate's launches; -1 without. */
+#define SCROLL_DYN_LOC_NONE    0
+#define SCROLL_DYN_LOC_FIT     1
+#define SCROLL_DYN_LOC_OVER    2
+#define SCROLL_DYN_LOC_NOFRAME 3
+typedef struct {
+    int16_t  x0, y0;               /* placed origin in MBs; x0 = -1: none */
+    uint16_t bx0, by0, bx1, by1;   /* the box after the margin, [bx0,bx1) x [by0,by1); 0 when none */
+    uint16_t status, reserved;     /* SCROLL_DYN_LOC_* */
+    uint32_t n_mb, max_sse;
+    uint64_t sse_all, sse_out;
+} ScrollDynDamage;                 /* 40 bytes */
+typedef struct { uint32_t mb_sse, margin, apply, reserved; } ScrollDynLocate;
+int scroll_batch_dyn_locate(ScrollBatch *b, int nframes, const ScrollSurfaces *surf,
+                            const ScrollDynLocate *rule, void *hip_stream);
+int scroll_batch_dyn_locate_result(ScrollBatch *b, int s, int f, ScrollDynDamage *out);   /* synchronising */
+const ScrollDynDamage *scroll_batch_dyn_locate_device(ScrollBatch *b, size_t *stream_stride);
+int scroll_batch_dyn_damage_map(ScrollBatch *b, int s, int f, uint32_t *dst);             /* mbw*mbh, synchronising */
+const uint32_t *scroll_batch_dyn_damage_map_device(ScrollBatch *b, size_t *stream_stride, size_t *frame_stride);
+float scroll_batch_dyn_locate_ms(ScrollBatch *b);   /* with enable_timing; -1 without */
+float scroll_batch_dyn_locate_kernel_ms(ScrollBatch *b);   /* the same for k_dyn_damage alone */
+
 /* Composer-level batch: offsets[i] composed on cs[i], i < n, in
  * order; Composers may repeat.  Output lands in each Composer's buffer before
  * return (equivalent to n composer_write_scroll_frame calls + a flush). */
