@@ -8,6 +8,7 @@
  *   batch_ingest.hip  ingest, I_PCM files, reference updates
  *   batch_surface.hip pixels from RGBA / BGRA surfaces: the rect's source, I420 pictures, device references
  *   batch_damage.hip  the rect located from the surfaces: damage map, placement, the positions' device ownership
+ *   batch_mask.hip    the rect's per-MB source mask: difference map, keep decision, fill
  *   batch_dropin.hip  the synchronous drop-in helpers of engine.h
  * Nothing here enters the library's dynamic symbol table.
  */
@@ -148,6 +149,24 @@ struct ScrollBatch {
         hipEvent_t ev[4] = {};          /* timing: the call's start, around k_dyn_damage, its end (created on first use) */
         int timed = 0;
     } lc;
+    /* the rect's per-MB source mask (scroll_batch_dyn_mask, batch_mask.hip,
+     * mask_kernels.hip): a dry plan and its prediction rows as the probe keeps
+     * them, the map, the rows' chroma partials and the records; nothing here
+     * exists before the first mask, everything goes with the rect */
+    struct Mask {
+        NalDesc *nal = nullptr;
+        DynFrame *dfr = nullptr;
+        PlanPending *pend = nullptr;
+        uint32_t *rows = nullptr, *ctr = nullptr;
+        uint4 *heads = nullptr;
+        uint32_t *map = nullptr;        /* [max_streams * max_frames][h][w][2] */
+        unsigned long long *part = nullptr;   /* [max_streams * max_frames][h][2]: Cb, Cr dropped per rect row */
+        ScrollDynMask *res = nullptr;   /* [max_streams * max_frames] */
+        int nframes = -1, nstreams = 0; /* the last mask; nframes -1: none */
+        hipEvent_t fin = nullptr;       /* recorded after the last mask's launches */
+        hipEvent_t ev[4] = {};          /* timing: the call's start, around k_dyn_mask_diff, its end (created on first use) */
+        int timed = 0;
+    } mk;
     /* UI hints: staged like the dynamic rect (shares
      * d_dfr, d_stage and geo.slot_bytes; the two are exclusive) */
     int hint_on = 0;
@@ -309,6 +328,9 @@ void locate_release(ScrollBatch *b);
  * locate has placed frames on the device, wait for it and read the table
  * back (synchronising); otherwise nothing */
 int dyn_pos_refresh(ScrollBatch *b);
+
+/* ---- batch_mask.hip ---- */
+void mask_release(ScrollBatch *b);
 
 }  // namespace batch
 }  // namespace scroll

@@ -542,6 +542,7 @@ void scroll_batch_destroy(ScrollBatch *b)
         if (e) (void)hipEventDestroy(e);
     probe_release(b);
     locate_release(b);
+    mask_release(b);
     (void)hipFree(b->dx.qpf);
     rate_release(b);
     surface_release(b, true);

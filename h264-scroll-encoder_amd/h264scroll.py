@@ -169,6 +169,21 @@ class ScrollDynLocate(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+SCROLL_DYN_MASK_OK, SCROLL_DYN_MASK_NOFRAME = 0, 1
+SCROLL_DYN_MASK_KEPT = 0x80000000
+
+
+class ScrollDynMaskRule(ctypes.Structure):
+    _fields_ = [("mb_sse_y", ctypes.c_uint32), ("mb_sse_c", ctypes.c_uint32), ("grow", ctypes.c_uint8),
+                ("apply", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 2)]
+
+
+class ScrollDynMask(ctypes.Structure):
+    """include/composer_batch.h: one frame's record of scroll_batch_dyn_mask"""
+    _fields_ = [("status", ctypes.c_int32), ("n_changed", ctypes.c_uint32), ("n_kept", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("sse_drop", ctypes.c_uint64 * 3)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} not built: run `make -C h264-scroll-encoder_amd` "
@@ -326,6 +341,17 @@ def _load():
                                                                  P(ctypes.c_size_t)]),
         "scroll_batch_dyn_locate_ms": (ctypes.c_float, [ctypes.c_void_p]),
         "scroll_batch_dyn_locate_kernel_ms": (ctypes.c_float, [ctypes.c_void_p]),
+        "scroll_batch_dyn_mask": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, P(ScrollDynMaskRule),
+                                                 ctypes.c_void_p]),
+        "scroll_batch_dyn_mask_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                        P(ScrollDynMask)]),
+        "scroll_batch_dyn_mask_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t)]),
+        "scroll_batch_dyn_mask_map": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                     P(ctypes.c_uint32)]),
+        "scroll_batch_dyn_mask_map_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t),
+                                                               P(ctypes.c_size_t)]),
+        "scroll_batch_dyn_mask_ms": (ctypes.c_float, [ctypes.c_void_p]),
+        "scroll_batch_dyn_mask_kernel_ms": (ctypes.c_float, [ctypes.c_void_p]),
         "composer_batch_write_scroll_frames": (ctypes.c_int, [P(P(Composer)), P(ctypes.c_int),
                                                               ctypes.c_int, ctypes.c_int]),
         "composer_flush": (ctypes.c_int, [P(Composer)]),
@@ -858,6 +884,61 @@ class Batch:
         (kernel: of k_dyn_damage alone); -1 without"""
         return (lib.scroll_batch_dyn_locate_kernel_ms if kernel else lib.scroll_batch_dyn_locate_ms)(self.h)
 
+    # ---- only the changed MBs of the rect are coded: the per-MB source mask ----
+    def dyn_mask(self, nframes, mb_sse_y=0, mb_sse_c=0, grow=0, apply=True, stream=None):
+        """frames 0 .. nframes - 1 of every stream: every MB of the rect's
+        source against the prediction a decoder forms for it
+        (scroll_batch_dyn_mask).  An MB changed when its luma squared error
+        exceeds mb_sse_y or its chroma one (Cb + Cr) mb_sse_c; MBs within
+        `grow` MBs (0..2) of a changed one are kept.  apply: the source of
+        every other MB becomes its prediction, so that dyn_probe, dyn_pick
+        and compose on the same `stream` code it without residual.
+        Asynchronous on `stream`, which is the source step's before it"""
+        rule = ScrollDynMaskRule(int(mb_sse_y), int(mb_sse_c), int(grow), int(apply))
+        self._chk(lib.scroll_batch_dyn_mask(self.h, nframes, ctypes.byref(rule), stream), "dyn_mask")
+
+    def dyn_mask_result(self, nframes):
+        """the last dyn_mask's records: a numpy structured array [S][nframes]
+        with ScrollDynMask's fields (status SCROLL_DYN_MASK_*; sse_drop: Y, Cb,
+        Cr).  Synchronises"""
+        import numpy as np
+        out = np.zeros((self.num_streams, nframes), dtype=_mask_dtype())
+        r = ScrollDynMask()
+        for s in range(out.shape[0]):
+            for f in range(nframes):
+                self._chk(lib.scroll_batch_dyn_mask_result(self.h, s, f, ctypes.byref(r)), "dyn_mask_result")
+                out[s, f] = (r.status, r.n_changed, r.n_kept, r.reserved, tuple(r.sse_drop))
+        return out
+
+    def dyn_mask_map(self, nframes, w, h):
+        """the last dyn_mask's map for the w x h rect: uint32 [S][nframes][h][w][2],
+        { Dy, Dc | SCROLL_DYN_MASK_KEPT } per MB.  Synchronises"""
+        import numpy as np
+        out = np.zeros((self.num_streams, nframes, h, w, 2), dtype=np.uint32)
+        for s in range(out.shape[0]):
+            for f in range(nframes):
+                self._chk(lib.scroll_batch_dyn_mask_map(self.h, s, f,
+                                                        out[s, f].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
+                          "dyn_mask_map")
+        return out
+
+    def dyn_mask_device(self):
+        """(device pointer, stream stride in bytes) of the records, ScrollDynMask [stream][frame]"""
+        ls = ctypes.c_size_t()
+        p = lib.scroll_batch_dyn_mask_device(self.h, ctypes.byref(ls))
+        return p, ls.value
+
+    def dyn_mask_map_device(self):
+        """(device pointer, stream stride, frame stride in bytes) of the map, uint32 [stream][frame][h][w][2]"""
+        ls, lf = ctypes.c_size_t(), ctypes.c_size_t()
+        p = lib.scroll_batch_dyn_mask_map_device(self.h, ctypes.byref(ls), ctypes.byref(lf))
+        return p, ls.value, lf.value
+
+    def dyn_mask_ms(self, kernel=False):
+        """with enable_timing: HIP-event ms of the last dyn_mask's launches
+        (kernel: of k_dyn_mask_diff alone); -1 without"""
+        return (lib.scroll_batch_dyn_mask_kernel_ms if kernel else lib.scroll_batch_dyn_mask_ms)(self.h)
+
     def dyn_source_synth(self, nframes, stream_base=0, t0=0):
         self._chk(lib.scroll_batch_dyn_source_synth(self.h, nframes, stream_base, t0),
                   "dyn_source_synth")
@@ -1063,6 +1144,12 @@ def _damage_dtype():
     return np.dtype([("x0", np.int16), ("y0", np.int16), ("bx0", np.uint16), ("by0", np.uint16), ("bx1", np.uint16),
                      ("by1", np.uint16), ("status", np.uint16), ("reserved", np.uint16), ("n_mb", np.uint32),
                      ("max_sse", np.uint32), ("sse_all", np.uint64), ("sse_out", np.uint64)])
+
+
+def _mask_dtype():
+    import numpy as np
+    return np.dtype([("status", np.int32), ("n_changed", np.uint32), ("n_kept", np.uint32), ("reserved", np.uint32),
+                     ("sse_drop", np.uint64, 3)])
 
 
 def pick_qp(res, qps, max_bits):

@@ -898,6 +898,84 @@ const uint32_t *scroll_batch_dyn_damage_map_device(ScrollBatch *b, size_t *strea
 float scroll_batch_dyn_locate_ms(ScrollBatch *b);   /* with enable_timing; -1 without */
 float scroll_batch_dyn_locate_kernel_ms(ScrollBatch *b);   /* the same for k_dyn_damage alone */
 
+/* ---- only the changed MBs of the rect are coded: the per-MB source mask ----
+ * (docs/MASTER_DESIGN.md §6).  The rect is a box, and every MB
+ * of it is coded from whatever the source holds: where the renderer drew
+ * nothing new the coder still spends levels on the difference between a
+ * pristine surface and the lossy references.  The mask compares every rect MB
+ * of the source with the exact prediction a decoder forms for it
+ * (csrc/mask_device.h):
+ *     Dy = sum over the MB's 256 luma samples of (src - pred)^2
+ *     Dc = the same sum over its 64 + 64 chroma samples (Cb + Cr together)
+ * pred: what k_dyn_row subtracts -- full-pel luma, 1/8-pel bilinear chroma,
+ * waypoints resolved through their chains (half-pel chains included), at the
+ * frame's own rect position (the batch's, scroll_batch_set_dyn_rect_at's or the
+ * located one) and scroll_batch_set_offsets' offsets.
+ * An MB is changed iff Dy > mb_sse_y || Dc > mb_sse_c; it is kept iff a
+ * changed MB of the same rect lies within `grow` MBs of it in both directions
+ * (Chebyshev distance, 0..2; grow = 0: the changed MBs themselves).  With
+ * apply = 1 every sample of an MB that is not kept is replaced in the source
+ * by its prediction: the MB then quantises to all-zero levels, is coded with
+ * coded_block_pattern 0, and a decoder shows for it exactly what it shows for
+ * a scroll MB.  Kept MBs are not written.  Everything after it (the probe,
+ * the pick, the compose, the reconstruction) reads the source and follows.
+ *
+ *   scroll_batch_dyn_mask(b, nframes, &rule, hip_stream)
+ *       frames 0 .. nframes - 1 of every stream.  A dry state pass (nothing of
+ *       the batch's state changes), k_dyn_rows into buffers of the mask's own,
+ *       then k_dyn_mask_diff, k_dyn_mask_fill, k_dyn_mask_rec.  Asynchronous
+ *       on hip_stream (0 = the batch's own), which must be the stream of the
+ *       source step before it and of the probe / compose after it.
+ *       SCROLL_ERR_CONFIG without a dynamic rect with reference pictures and
+ *       with UI hints set; SCROLL_ERR_ARG for nframes outside 0..max_frames,
+ *       grow > 2, apply > 1 or a NULL rule.  A refused call writes nothing.
+ *       A frame without a dynamic NAL (no rect in it, experiment mode's
+ *       waypoint frame) gets SCROLL_DYN_MASK_NOFRAME, zero map entries and an
+ *       untouched source.  A second call with the same rule leaves the source
+ *       as it is (the MBs it dropped now have D = 0).  Buffers are allocated by
+ *       the first call and go with the rect; a batch that never calls it gains
+ *       no launch, allocation or changed byte.
+ *   the map: per frame w * h entries of two uint32, row by row over the rect's
+ *       MBs: { Dy, Dc | kept << 31 } (SCROLL_DYN_MASK_KEPT; Dc < 2^24).
+ *   the record: n_changed, n_kept, and sse_drop[Y, Cb, Cr] = the squared
+ *       error between the source as it was and the prediction, summed over
+ *       the MBs not kept: what the mask gives up, in scroll_batch_dyn_sse's
+ *       units (with the reconstruction on, dyn_sse after the mask + sse_drop is
+ *       the squared error of the decoded rect against the original source).
+ *       Every value is a sum or a count over the stored map: no atomics,
+ *       independent of order.
+ *   scroll_batch_dyn_mask_result / _mask_map   one frame's record / its map
+ *       (2 w h uint32; synchronising; SCROLL_ERR_CONFIG before the first mask,
+ *       SCROLL_ERR_ARG outside the last one)
+ *   scroll_batch_dyn_mask_device / _mask_map_device   the device arrays,
+ *       [stream][frame] records and [stream][frame][h][w][2] uint32 (strides
+ *       in bytes); NULL before the first mask
+ *   scroll_batch_dyn_mask_ms   with scroll_batch_enable_timing: HIP-event ms of
+ *       the last mask's launches; -1 without. */
+#define SCROLL_DYN_MASK_OK      0
+#define SCROLL_DYN_MASK_NOFRAME 1
+#define SCROLL_DYN_MASK_KEPT    0x80000000u   /* bit 31 of a map entry's second word */
+typedef struct {
+    uint32_t mb_sse_y;             /* an MB changed iff Dy > mb_sse_y ...                     */
+    uint32_t mb_sse_c;             /* ... or Dc > mb_sse_c (Cb + Cr together)                */
+    uint8_t  grow;                 /* 0..2: keep MBs within this Chebyshev distance of a changed MB */
+    uint8_t  apply;                /* 1: overwrite the source of MBs not kept; 0: report only */
+    uint8_t  reserved[2];
+} ScrollDynMaskRule;               /* 12 bytes */
+typedef struct {
+    int32_t  status;               /* SCROLL_DYN_MASK_* */
+    uint32_t n_changed, n_kept;
+    uint32_t reserved;
+    uint64_t sse_drop[3];          /* Y, Cb, Cr */
+} ScrollDynMask;                   /* 40 bytes */
+int scroll_batch_dyn_mask(ScrollBatch *b, int nframes, const ScrollDynMaskRule *rule, void *hip_stream);
+int scroll_batch_dyn_mask_result(ScrollBatch *b, int s, int f, ScrollDynMask *out);       /* synchronising */
+const ScrollDynMask *scroll_batch_dyn_mask_device(ScrollBatch *b, size_t *stream_stride);
+int scroll_batch_dyn_mask_map(ScrollBatch *b, int s, int f, uint32_t *dst);               /* 2*w*h, synchronising */
+const uint32_t *scroll_batch_dyn_mask_map_device(ScrollBatch *b, size_t *stream_stride, size_t *frame_stride);
+float scroll_batch_dyn_mask_ms(ScrollBatch *b);     /* with enable_timing; -1 without */
+float scroll_batch_dyn_mask_kernel_ms(ScrollBatch *b);     /* the same for k_dyn_mask_diff alone */
+
 /* Composer-level batch: offsets[i] composed on cs[i], i < n, in
  * order; Composers may repeat.  Output lands in each Composer's buffer before
  * return (equivalent to n composer_write_scroll_frame calls + a flush). */
