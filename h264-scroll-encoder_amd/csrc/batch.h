@@ -208,6 +208,16 @@ struct ScrollBatch {
      * device's table is the truth and h_dyn_pos / dyn_pos_custom are behind
      * until dyn_pos_refresh reads it back; never set together with dpos_stale */
     int dpos_dev = 0;
+    /* scroll_batch_set_dyn_rect_size_at: the columns and rows
+     * frame (s, f)'s rect is short of the batch's, [2 (s * max_frames + f)],
+     * empty until the first size is set -- apart from h_dyn_pos, which the
+     * hinted uploads read.  dsz_any: some entry is not 0 (as of the last
+     * change, or of the read-back of a located table); dsz_on: the row stage
+     * is sized for every h_f (done once, by the first call) */
+    std::vector<uint8_t> h_dyn_dsz;
+    size_t dsz_nz = 0;                 /* frames whose entry is not (0, 0): dsz_any without a scan */
+    int dsz_any = 0;
+    int dsz_on = 0;
     hipStream_t dpos_hs = nullptr;     /* the stream that upload ran on ... */
     hipEvent_t dpos_ev = nullptr;      /* ... and its end: other streams wait for it, the next packing too */
     int dyn_qp = 26;                   /* the rect's QP (scroll_batch_set_dyn_qp)          */
@@ -297,6 +307,17 @@ int dyn_set_refs(ScrollBatch *b, int s, const uint8_t *ref_a, const uint8_t *ref
  * (uploaded there first when stale), or NULL: the flag is off, or every
  * frame sits at the batch's position */
 int dyn_pos_table(ScrollBatch *b, hipStream_t hs, const uint32_t **dpos);
+/* entry i of the table as the host has it: origin and size packed (dyn_pos.h) */
+uint32_t dyn_pos_word(const ScrollBatch *b, size_t i);
+/* some frame has a size of its own (bringing the host's copy up to date
+ * first where a locate wrote the table): what the hinted paths refuse */
+int dyn_sizes_any(ScrollBatch *b, bool *any);
+/* before the first frame gets a size of its own (scroll_batch_set_dyn_rect_size_at,
+ * a locate with size = 1): the row stage, the groups' bit counts and the
+ * static grid for every legal (y0, h_f), allocated once; later calls do
+ * nothing.  SCROLL_ERR_CONFIG without scroll_batch_set_dyn_rect_moving or in
+ * a picture of more than 256 MBs either way */
+int dyn_sizes_enable(ScrollBatch *b, const char *who);
 
 /* ---- batch_rate.hip ---- */
 void rate_release(ScrollBatch *b);

@@ -705,6 +705,12 @@ int scroll_batch_compose_ex(ScrollBatch *b, int nframes, void *hip_stream, int f
         int rc = dyn_pos_refresh(b);
         if (rc) return rc;
     }
+    if (combined && b->dsz_any) {
+        /* (the host's copy is current: the refresh above) */
+        set_err("scroll_batch_compose: a frame has a size of its own (scroll_batch_set_dyn_rect_size_at), which "
+                "the rect under UI hints does not follow: clear the hints or the sizes");
+        return SCROLL_ERR_CONFIG;
+    }
     if (b->dyn_pos_custom && !b->hint_on && !b->dyn_moving) {
         set_err("scroll_batch_compose: per-frame dynamic rect positions need UI hints "
                 "(scroll_batch_set_hints)");

@@ -13,6 +13,7 @@
 #include "scroll_engine.h"
 #include "csc_device.h"
 #include "damage_engine.h"
+#include "dyn_pos.h"            /* dyn_pos_unpack: the position table's word */
 
 using namespace scroll::batch;
 
@@ -49,13 +50,25 @@ int dyn_pos_refresh(ScrollBatch *b)
     b->h_dpos.resize(n);
     HIPCHK(hipMemcpy(b->h_dpos.data(), b->d_dpos, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     bool any = false;
+    size_t sized = 0;
     for (size_t i = 0; i < n; ++i) {
         const uint32_t e = b->h_dpos[i];
-        const int32_t x = e == DYN_POS_NONE ? -1 : (int32_t)(e & 0xffffu), y = e == DYN_POS_NONE ? -1 : (int32_t)(e >> 16);
+        const DynPosWord p = dyn_pos_unpack(e == DYN_POS_NONE ? 0u : e, b->geo.pos_mask);
+        const int32_t x = e == DYN_POS_NONE ? -1 : p.x0, y = e == DYN_POS_NONE ? -1 : p.y0;
         b->h_dyn_pos[2 * i] = x;
         b->h_dyn_pos[2 * i + 1] = y;
         any |= x != b->geo.x0 || (x >= 0 && y != b->geo.y0);
+        /* the size a locate with size = 1 gave the frame (only a batch whose
+         * row stage is sized for it gets such entries: dsz_on) */
+        if (!b->h_dyn_dsz.empty()) {
+            b->h_dyn_dsz[2 * i] = (uint8_t)p.dw;
+            b->h_dyn_dsz[2 * i + 1] = (uint8_t)p.dh;
+            sized += (p.dw | p.dh) != 0 ? 1 : 0;
+        }
     }
+    b->dsz_nz = sized;
+    b->dsz_any = sized ? 1 : 0;
+    any |= sized != 0;
     /* host and device agree again: nothing to upload */
     b->dyn_pos_custom = any ? 1 : 0;
     b->dpos_any = any ? 1 : 0;
@@ -136,6 +149,11 @@ int scroll_batch_dyn_locate(ScrollBatch *b, int nframes, const ScrollSurfaces *s
         set_err("%s: margin %u above 4 or apply %u not 0 / 1", who, rule->margin, rule->apply);
         return SCROLL_ERR_ARG;
     }
+    if (rule->size > 1u || (rule->size && !rule->apply)) {
+        set_err("%s: size %u not 0 / 1, or size = 1 without apply = 1 (a size is placed with its origin)", who,
+                rule->size);
+        return SCROLL_ERR_ARG;
+    }
     const int rc = surf_args(who, surf, (uint64_t)b->dyn_pw, true);
     if (rc) return rc;
     if (surf->cropped) {
@@ -145,6 +163,11 @@ int scroll_batch_dyn_locate(ScrollBatch *b, int nframes, const ScrollSurfaces *s
     if (rule->apply && !b->dyn_moving) {
         set_err("%s: apply = 1 places the rect per frame: needs scroll_batch_set_dyn_rect_moving", who);
         return SCROLL_ERR_CONFIG;
+    }
+    if (rule->size) {
+        /* the row stage for every h_f, once (no later locate allocates) */
+        const int sr = dyn_sizes_enable(b, who);
+        if (sr) return sr;
     }
     const int S = b->nstreams, ld_fr = b->max_frames;
     const uint32_t mbw = (uint32_t)b->dyn_pw / 16u, mbh = (uint32_t)b->dyn_ph / 16u;
@@ -187,8 +210,7 @@ int scroll_batch_dyn_locate(ScrollBatch *b, int nframes, const ScrollSurfaces *s
             const size_t n = (size_t)b->max_streams * b->max_frames;
             b->h_dpos.resize(n);
             for (size_t i = 0; i < n; ++i) {
-                const int32_t x = b->h_dyn_pos[2 * i], y = b->h_dyn_pos[2 * i + 1];
-                b->h_dpos[i] = x < 0 ? DYN_POS_NONE : (uint32_t)x | (uint32_t)y << 16;
+                b->h_dpos[i] = dyn_pos_word(b, i);
             }
             HIPCHK(hipMemcpyAsync(b->d_dpos, b->h_dpos.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, hs));
         } else if (hs != b->dpos_hs) {

@@ -16,6 +16,7 @@
 #include "probe_engine.h"
 #include "hprobe_engine.h"
 #include "hdyn_engine.h"        /* HDYN_MB_WORDS_*: pool words per rect MB under hints */
+#include "dyn_pos.h"            /* dyn_pos_pack: the position table's word */
 #include "dyn_device.h"         /* scroll::dyn::qparams, qp_chroma: DynGeom's quantisers */
 
 using namespace scroll::batch;
@@ -78,6 +79,10 @@ void dyn_release(ScrollBatch *b)
     b->dyn_moving = 0;
     b->dpos_stale = 1;
     b->dpos_any = 0;
+    b->h_dyn_dsz.clear();              /* sizes go with the rect */
+    b->dsz_nz = 0;
+    b->dsz_any = 0;
+    b->dsz_on = 0;
     rate_release(b);
     surface_release(b, false);
     (void)hipFree(b->d_rec);           /* the reconstruction goes with the rect it was sized for */
@@ -317,6 +322,66 @@ int dyn_set_refs(ScrollBatch *b, int s, const uint8_t *ref_a, const uint8_t *ref
     return SCROLL_OK;
 }
 
+uint32_t dyn_pos_word(const ScrollBatch *b, size_t i)
+{
+    const int32_t x = b->h_dyn_pos[2 * i], y = b->h_dyn_pos[2 * i + 1];
+    if (x < 0) return DYN_POS_NONE;
+    const bool sz = !b->h_dyn_dsz.empty();
+    return dyn_pos_pack((uint32_t)x, (uint32_t)y, sz ? b->h_dyn_dsz[2 * i] : 0u, sz ? b->h_dyn_dsz[2 * i + 1] : 0u);
+}
+
+int dyn_sizes_any(ScrollBatch *b, bool *any)
+{
+    *any = false;
+    if (!b->dyn_on || !b->dsz_on) return SCROLL_OK;
+    const int rc = dyn_pos_refresh(b);
+    if (rc) return rc;
+    *any = b->dsz_any != 0;
+    return SCROLL_OK;
+}
+
+int dyn_sizes_enable(ScrollBatch *b, const char *who)
+{
+    if (!b->dyn_moving) {
+        set_err("%s: a frame's own size needs scroll_batch_set_dyn_rect_moving", who);
+        return SCROLL_ERR_CONFIG;
+    }
+    if (b->geo.pos_mask != 0xffu) {
+        set_err("%s: a frame's own size needs a picture of at most 256 x 256 MBs (the table word's origin bytes)", who);
+        return SCROLL_ERR_CONFIG;
+    }
+    if (b->dsz_on) return SCROLL_OK;
+    int rc = batch_host_sync(b);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(b->device));
+    if (b->pb.fin) HIPCHK(hipEventSynchronize(b->pb.fin));     /* a probe on another stream */
+    if (b->dpos_ev) HIPCHK(hipEventSynchronize(b->dpos_ev));   /* an upload or a locate */
+    DynGeom g = b->geo;
+    dyn_rowstage_geom(&g, b->dyn_pw / 16, b->dyn_ph / 16, 2);
+    const size_t S = (size_t)b->max_streams, F = (size_t)b->max_frames;
+    const size_t rs_words = S * F * g.rs_frame_words + (size_t)g.rs_spill_cap * g.rs_spill_words;
+    uint32_t *rs = nullptr, *gbits = nullptr;
+    hipError_t e = hipMalloc(&rs, rs_words * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&gbits, S * F * (size_t)g.ld_groups * sizeof(uint32_t));
+    if (e != hipSuccess) {
+        (void)hipFree(rs);
+        (void)hipFree(gbits);
+        return hip_fail(who, e, true);
+    }
+    (void)hipFree(b->dx.rowstage);
+    (void)hipFree(b->dx.gbits);
+    b->dx.rowstage = rs;
+    b->dx.spill = rs + S * F * g.rs_frame_words;
+    b->dx.gbits = gbits;
+    g.dpos = nullptr;
+    b->geo = g;
+    b->h_dyn_dsz.assign(2 * S * F, 0);
+    b->dsz_nz = 0;
+    b->dsz_any = 0;
+    b->dsz_on = 1;
+    return SCROLL_OK;
+}
+
 int dyn_pos_table(ScrollBatch *b, hipStream_t hs, const uint32_t **dpos)
 {
     *dpos = nullptr;
@@ -332,8 +397,9 @@ int dyn_pos_table(ScrollBatch *b, hipStream_t hs, const uint32_t **dpos)
         for (size_t i = 0; i < n; ++i) {
             const int32_t x = b->h_dyn_pos[2 * i], y = b->h_dyn_pos[2 * i + 1];
             any |= x != b->geo.x0 || (x >= 0 && y != b->geo.y0);
-            b->h_dpos[i] = x < 0 ? DYN_POS_NONE : (uint32_t)x | (uint32_t)y << 16;
+            b->h_dpos[i] = dyn_pos_word(b, i);
         }
+        any |= b->dsz_any != 0;                         /* a frame sized on its own */
         b->dpos_hs = nullptr;
         if (any) {
             HIPCHK(hipMemcpyAsync(b->d_dpos, b->h_dpos.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, hs));
@@ -391,8 +457,10 @@ int scroll_batch_set_dyn_rect(ScrollBatch *b, int x0, int y0, int w, int h, size
     g.y0 = y0;
     g.pw = pw;
     g.ph = ph;
-    g.w = w;
-    g.h = h;
+    g.w = g.ld_w = w;
+    g.h = g.ld_h = h;
+    /* origins below 256 leave a table word's high bytes to the frames' sizes */
+    g.pos_mask = mbw <= 256 && mbh <= 256 ? 0xffu : 0xffffu;
     g.qp = b->dyn_qp;
     g.ql = scroll::dyn::qparams(g.qp);
     g.qc = scroll::dyn::qparams(scroll::dyn::qp_chroma(g.qp));
@@ -521,6 +589,12 @@ int scroll_batch_set_dyn_rect_moving(ScrollBatch *b, int on)
     if (b->pb.fin) HIPCHK(hipEventSynchronize(b->pb.fin));     /* a probe on another stream */
     if (b->dpos_ev) HIPCHK(hipEventSynchronize(b->dpos_ev));
     if ((rc = dyn_pos_refresh(b))) return rc;                   /* located positions outlive the table */
+    if (!on && b->dsz_on) {                                     /* sizes need the flag: they go with it */
+        b->h_dyn_dsz.clear();
+        b->dsz_nz = 0;
+        b->dsz_any = 0;
+        b->dsz_on = 0;
+    }
     DynGeom g = b->geo;
     dyn_rowstage_geom(&g, b->dyn_pw / 16, b->dyn_ph / 16, on ? 1 : 0);
     const size_t S = (size_t)b->max_streams, F = (size_t)b->max_frames;
@@ -552,6 +626,39 @@ int scroll_batch_set_dyn_rect_moving(ScrollBatch *b, int on)
     g.dpos = nullptr;
     b->geo = g;
     b->dyn_moving = on ? 1 : 0;
+    return SCROLL_OK;
+}
+
+/* The plain rect sized per stream and per frame: frame f of
+ * stream s codes w x h MBs at its own origin.  The table's word carries the
+ * difference to the batch's size, so a batch that never calls this uploads
+ * the words it always did. */
+int scroll_batch_set_dyn_rect_size_at(ScrollBatch *b, int s, int f, int w, int h)
+{
+    const char *who = "scroll_batch_set_dyn_rect_size_at";
+    if (!b || !b->dyn_on || s < 0 || s >= b->nstreams || f < 0 || f >= b->max_frames) {
+        set_err("%s: no dynamic rect, or stream / frame out of range", who);
+        return SCROLL_ERR_ARG;
+    }
+    if (w < 1 || w > b->geo.w || h < 1 || h > b->geo.h) {
+        set_err("%s: size %d x %d outside 1..%d x 1..%d (scroll_batch_set_dyn_rect's size)", who, w, h, b->geo.w,
+                b->geo.h);
+        return SCROLL_ERR_ARG;
+    }
+    int rc = dyn_sizes_enable(b, who);
+    if (rc) return rc;
+    if ((rc = batch_host_sync(b))) return rc;
+    /* a probe on a stream of its own may still read the device table */
+    if (b->pb.fin) HIPCHK(hipEventSynchronize(b->pb.fin));
+    /* what a locate placed on the device stays, all but this frame's size */
+    if ((rc = dyn_pos_refresh(b))) return rc;
+    const size_t i = (size_t)s * b->max_frames + f;
+    const bool was = (b->h_dyn_dsz[2 * i] | b->h_dyn_dsz[2 * i + 1]) != 0, is = w != b->geo.w || h != b->geo.h;
+    b->h_dyn_dsz[2 * i] = (uint8_t)(b->geo.w - w);
+    b->h_dyn_dsz[2 * i + 1] = (uint8_t)(b->geo.h - h);
+    b->dsz_nz = b->dsz_nz - (was ? 1 : 0) + (is ? 1 : 0);      /* no scan of the other frames' entries */
+    b->dsz_any = b->dsz_nz ? 1 : 0;
+    b->dpos_stale = 1;
     return SCROLL_OK;
 }
 
@@ -933,6 +1040,13 @@ int scroll_batch_dyn_probe_hinted(ScrollBatch *b, int nframes, const uint8_t *qp
         return SCROLL_ERR_CONFIG;
     }
     HIPCHK(hipSetDevice(b->device));
+    bool sized = false;
+    if ((rc = dyn_sizes_any(b, &sized))) return rc;
+    if (sized) {
+        set_err("scroll_batch_dyn_probe_hinted: a frame has a size of its own (scroll_batch_set_dyn_rect_size_at), "
+                "which the rect under UI hints does not follow: clear the hints or the sizes");
+        return SCROLL_ERR_CONFIG;
+    }
     if (b->hd_dirty && (rc = hd_upload(b))) return rc;
     if (b->hint_dirty && (rc = hint_upload(b))) return rc;
     if ((rc = probe_alloc(b))) return rc;

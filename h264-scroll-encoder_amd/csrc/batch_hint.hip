@@ -358,13 +358,16 @@ int scroll_batch_clear_hints(ScrollBatch *b)
             return hip_fail("scroll_batch_clear_hints", e);
         }
         b->geo.slot_bytes = b->dyn_cap;
-        if (b->dyn_pos_custom || b->dpos_dev) {            /* (located positions go too, unread) */
+        if (b->dyn_pos_custom || b->dpos_dev || b->dsz_any) {   /* (located positions and sizes go too, unread) */
             if (b->dpos_dev) HIPCHK(hipEventSynchronize(b->dpos_ev));
             b->dpos_dev = 0;
             for (size_t i = 0; i < S * F; ++i) {
                 b->h_dyn_pos[2 * i] = b->geo.x0;
                 b->h_dyn_pos[2 * i + 1] = b->geo.y0;
             }
+            std::fill(b->h_dyn_dsz.begin(), b->h_dyn_dsz.end(), (uint8_t)0);   /* sizes go with the positions */
+            b->dsz_nz = 0;
+            b->dsz_any = 0;
             b->dyn_pos_custom = 0;
             b->dpos_stale = 1;
         }

@@ -141,9 +141,18 @@ int scroll_batch_dyn_source_from_surfaces(ScrollBatch *b, int nframes, const Scr
         const int pr = dyn_pos_refresh(b);
         if (pr) return pr;
     }
+    job.pos_mask = g.pos_mask;
     if (located) {
         if (hs != b->dpos_hs) HIPCHK(hipStreamWaitEvent(hs, b->dpos_ev, 0));   /* located on another stream */
         job.dpos = b->d_dpos;
+        job.dpos_ld = (uint32_t)b->max_frames;
+    } else if (b->dsz_any && b->dyn_moving && !b->hint_on) {
+        /* frames sized on their own: origins and sizes in the
+         * packed table the coder's kernels read, uploaded here when stale */
+        const uint32_t *dp = nullptr;
+        const int pr = dyn_pos_table(b, hs, &dp);
+        if (pr) return pr;
+        job.dpos = dp;
         job.dpos_ld = (uint32_t)b->max_frames;
     } else if (b->dyn_pos_custom) {
         /* the origins of this call's frames, compact; the table is the

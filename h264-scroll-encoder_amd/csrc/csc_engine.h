@@ -26,6 +26,11 @@ typedef struct {
      * form: x0 | y0 << 16, DYN_POS_NONE: skipped), item (s, f) at dpos[s dpos_ld + f] */
     const uint32_t *dpos;
     uint32_t dpos_ld;
+    /* DynGeom.pos_mask of that table (0: as 0xffff).  At 0xff an entry's high
+     * bytes hold (w - w_f) / 16 and (h - h_f) / 16: the item
+     * then crops w_f x h_f pixels into the layout of a w_f x h_f picture at
+     * the head of its block, whose stride stays dst_fr */
+    uint32_t pos_mask;
     int32_t x0, y0;
     uint32_t w, h;
     uint32_t S, nframes;

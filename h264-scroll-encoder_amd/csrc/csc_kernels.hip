@@ -58,17 +58,20 @@ __global__ __launch_bounds__(CSC_T) void k_csc(CscArgs a)
 {
     const CscJob &j = a.j;
     const uint32_t stride = gridDim.x * CSC_T;
-    const uint64_t plane = (uint64_t)j.w * j.h;
     for (uint32_t t = blockIdx.x * CSC_T + threadIdx.x; t < a.total; t += stride) {
         uint32_t r, cg, f;
         const uint32_t item = divmod(t, a.tpi, a.m_tpi, &r);
         const uint32_t rp = divmod(r, a.cw, a.m_cw, &cg);
         const uint32_t s = divmod(item, j.nframes, a.m_nf, &f);
         int32_t x0 = j.x0, y0 = j.y0;
+        uint32_t w = j.w, h = j.h;      /* the item's own window */
         if (j.dpos) {
             const uint32_t e = j.dpos[(uint64_t)s * j.dpos_ld + f];
-            x0 = e == 0xFFFFFFFFu ? -1 : (int32_t)(e & 0xFFFFu);
-            y0 = (int32_t)(e >> 16);
+            const uint32_t pm = j.pos_mask ? j.pos_mask : 0xFFFFu, lo = e & 0xFFFFu, hi = e >> 16;
+            x0 = e == 0xFFFFFFFFu ? -1 : (int32_t)(lo & pm);
+            y0 = (int32_t)(hi & pm);
+            w -= 16u * ((lo & ~pm) >> 8);
+            h -= 16u * ((hi & ~pm) >> 8);
         } else if (j.pos) {
             /* (x, y) in one 8-byte load */
             const uint64_t p = reinterpret_cast<const uint64_t *>(j.pos)[(uint64_t)s * j.nframes + f];
@@ -76,6 +79,8 @@ __global__ __launch_bounds__(CSC_T) void k_csc(CscArgs a)
             y0 = (int32_t)(uint32_t)(p >> 32);
         }
         if (x0 < 0) continue;           /* no rect in this frame: its block stays */
+        if (2u * rp >= h || 8u * cg >= w) continue;     /* past a sized frame's own window */
+        const uint64_t plane = (uint64_t)w * h;
         if (j.cropped) x0 = y0 = 0;
         const uint8_t *sp = j.src + (uint64_t)s * j.src_ld + (uint64_t)f * j.src_fr +
                             ((uint64_t)(16u * (uint32_t)y0) + 2u * rp) * j.pitch +
@@ -86,14 +91,14 @@ __global__ __launch_bounds__(CSC_T) void k_csc(CscArgs a)
         const uint4 b1 = *reinterpret_cast<const uint4 *>(sp + j.pitch + 16);
 
         uint8_t *dp = j.dst + (uint64_t)s * j.dst_ld + (uint64_t)f * j.dst_fr;
-        uint8_t *yp = dp + (uint64_t)(2u * rp) * j.w + 8u * cg;
+        uint8_t *yp = dp + (uint64_t)(2u * rp) * w + 8u * cg;
         *reinterpret_cast<uint2 *>(yp) = make_uint2(luma4(j.k, t0), luma4(j.k, t1));
-        *reinterpret_cast<uint2 *>(yp + j.w) = make_uint2(luma4(j.k, b0), luma4(j.k, b1));
+        *reinterpret_cast<uint2 *>(yp + w) = make_uint2(luma4(j.k, b0), luma4(j.k, b1));
 
         uint32_t cb = 0, cr = 0;
         chroma2(j.k, t0, b0, 0, &cb, &cr);
         chroma2(j.k, t1, b1, 16, &cb, &cr);
-        uint8_t *cp = dp + plane + (uint64_t)rp * (j.w >> 1) + 4u * cg;
+        uint8_t *cp = dp + plane + (uint64_t)rp * (w >> 1) + 4u * cg;
         *reinterpret_cast<uint32_t *>(cp) = cb;
         *reinterpret_cast<uint32_t *>(cp + (plane >> 2)) = cr;
     }

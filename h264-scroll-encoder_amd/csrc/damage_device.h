@@ -45,6 +45,16 @@
  *   outside the placed rect (= sse_all without one), max_sse = the largest D.
  * Every value is a sum, a count, a minimum or a maximum: independent of the
  * order in which the MBs are visited.
+ *
+ * With size = 1 (ScrollDynLocate.size) the placed rect is also
+ * sized: from the same origin it reaches to the box's end or to the batch
+ * size, whichever comes first,
+ *   w_f = min(bx1, x0 + w) - x0,   h_f = min(by1, y0 + h) - y0
+ * so a FIT rect covers exactly origin-to-box-end and an OVER rect is w x h in
+ * the dimension that is over.  The record's reserved word then holds
+ * (w_f - 1) | (h_f - 1) << 8 (0 without a rect), sse_out is summed outside
+ * the sized rect, and the table's entry carries w - w_f, h - h_f
+ * (dyn_pos_pack).  size = 0: every value as before, reserved 0.
  */
 #ifndef SCROLL_DAMAGE_DEVICE_H
 #define SCROLL_DAMAGE_DEVICE_H
@@ -139,7 +149,7 @@ __host__ __device__ inline ScrollDynDamage noframe()
 /* the record of a frame from its whole map's Acc, all but sse_out, which is
  * sse_all until outside() has been summed (finish) */
 __host__ __device__ inline ScrollDynDamage place(const Acc &a, uint32_t w, uint32_t h, uint32_t mbw, uint32_t mbh,
-                                                 uint32_t margin)
+                                                 uint32_t margin, uint32_t size = 0u)
 {
     ScrollDynDamage r{};
     r.n_mb = a.n;
@@ -157,10 +167,25 @@ __host__ __device__ inline ScrollDynDamage place(const Acc &a, uint32_t w, uint3
     r.status = bx1 - bx0 <= w && by1 - by0 <= h ? SCROLL_DYN_LOC_FIT : SCROLL_DYN_LOC_OVER;
     r.x0 = (int16_t)minu(bx0, mbw - w);
     r.y0 = (int16_t)minu(by0, mbh - h);
+    if (size) {
+        const uint32_t x0 = (uint32_t)r.x0, y0 = (uint32_t)r.y0;
+        const uint32_t wf = minu(bx1, x0 + w) - x0, hf = minu(by1, y0 + h) - y0;
+        r.reserved = (uint16_t)((wf - 1u) | (hf - 1u) << 8);
+    }
     return r;
 }
 
-/* MB (mx, my) lies inside the w x h rect the record places */
+/* the size of the rect a record places: the batch's w x h, or with size = 1 its own */
+__host__ __device__ inline uint32_t placed_w(const ScrollDynDamage &r, uint32_t w, uint32_t size)
+{
+    return size && r.x0 >= 0 ? (r.reserved & 255u) + 1u : w;
+}
+__host__ __device__ inline uint32_t placed_h(const ScrollDynDamage &r, uint32_t h, uint32_t size)
+{
+    return size && r.x0 >= 0 ? (uint32_t)(r.reserved >> 8) + 1u : h;
+}
+
+/* MB (mx, my) lies inside the w x h rect the record places (w, h: placed_w, placed_h) */
 __host__ __device__ inline bool covered(const ScrollDynDamage &r, uint32_t w, uint32_t h, uint32_t mx, uint32_t my)
 {
     if (r.x0 < 0) return false;
@@ -176,19 +201,28 @@ __host__ __device__ inline uint32_t pos_entry(const ScrollDynDamage &r)
 {
     return r.x0 < 0 ? 0xFFFFFFFFu : (uint32_t)r.x0 | (uint32_t)r.y0 << 16;
 }
+/* ... of a record placed with size = 1 in a batch whose rect is w x h: the
+ * columns and rows the frame's rect is short of it in bits 8-15 and 24-31 */
+__host__ __device__ inline uint32_t pos_entry_sized(const ScrollDynDamage &r, uint32_t w, uint32_t h)
+{
+    if (r.x0 < 0) return 0xFFFFFFFFu;
+    return pos_entry(r) | (w - placed_w(r, w, 1u)) << 8 | (h - placed_h(r, h, 1u)) << 24;
+}
 
 /* one frame, serially: the rule as a whole, for the CPU and for reading */
 __host__ __device__ inline ScrollDynDamage locate_frame(const uint32_t *map, uint32_t w, uint32_t h, uint32_t mbw,
-                                                        uint32_t mbh, uint32_t mb_sse, uint32_t margin)
+                                                        uint32_t mbh, uint32_t mb_sse, uint32_t margin,
+                                                        uint32_t size = 0u)
 {
     Acc a = acc_init();
     for (uint32_t my = 0; my < mbh; ++my)
         for (uint32_t mx = 0; mx < mbw; ++mx) acc_add(a, map[(size_t)my * mbw + mx], mx, my, mb_sse);
-    ScrollDynDamage r = place(a, w, h, mbw, mbh, margin);
+    ScrollDynDamage r = place(a, w, h, mbw, mbh, margin, size);
+    const uint32_t wf = placed_w(r, w, size), hf = placed_h(r, h, size);
     uint64_t in = 0;
     for (uint32_t my = 0; my < mbh; ++my)
         for (uint32_t mx = 0; mx < mbw; ++mx)
-            if (covered(r, w, h, mx, my)) in += map[(size_t)my * mbw + mx];
+            if (covered(r, wf, hf, mx, my)) in += map[(size_t)my * mbw + mx];
     finish(r, in);
     return r;
 }

@@ -172,19 +172,20 @@ __global__ __launch_bounds__(PLACE_T) void k_dyn_place(const DynFrame *__restric
     for (uint32_t i = t; i < nmb; i += PLACE_T) acc_add(a, m[i], i % mbw, i / mbw, rule.mb_sse);
     part[t] = a;
     reduce256(part, t, [](Acc &x, const Acc &y) { acc_merge(x, y); });
-    if (t == 0) rec = place(part[0], w, h, mbw, mbh, rule.margin);
+    if (t == 0) rec = place(part[0], w, h, mbw, mbh, rule.margin, rule.size);
     __syncthreads();
     ScrollDynDamage r = rec;
     uint64_t sum = 0;
+    const uint32_t wf = placed_w(r, w, rule.size), hf = placed_h(r, h, rule.size);   /* the rect as placed (and sized) */
     if (r.x0 >= 0)
-        for (uint32_t i = t; i < w * h; i += PLACE_T)
-            sum += m[((uint32_t)r.y0 + i / w) * mbw + (uint32_t)r.x0 + i % w];
+        for (uint32_t i = t; i < wf * hf; i += PLACE_T)
+            sum += m[((uint32_t)r.y0 + i / wf) * mbw + (uint32_t)r.x0 + i % wf];
     in[t] = sum;
     reduce256(in, t, [](uint64_t &x, const uint64_t &y) { x += y; });
     if (t == 0) {
         finish(r, in[0]);
         res[nb] = r;
-        if (dpos) dpos[nb] = pos_entry(r);
+        if (dpos) dpos[nb] = rule.size ? pos_entry_sized(r, w, h) : pos_entry(r);
     }
 }
 

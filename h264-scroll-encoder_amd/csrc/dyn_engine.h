@@ -88,7 +88,10 @@ int dyn_launch_synth(hipStream_t hs, int nframes, int S, uint8_t *src, const Dyn
 
 /* row groups (ngroups, ld_groups) and row-stage geometry (rs_* fields) of a
  * rect in an mbw x mbh picture; moving: sized for every legal y0 (ld_groups
- * the most groups of any, a static group's slot for the most rows of any) */
+ * the most groups of any, a static group's slot for the most rows of any);
+ * moving = 2: for every legal y0 and every rect height 1..h as well (frames
+ * sized on their own: ld_groups, ld_static and rs_frame_words each the
+ * largest over all of them, dyn_sized_max) */
 void dyn_rowstage_geom(DynGeom *g, int mbw, int mbh, int moving);
 /* staging bytes per frame that no dynamic NAL can exceed */
 size_t dyn_slot_bound(int mbw, int mbh, int rw, int rh);

@@ -279,6 +279,7 @@ __device__ inline void code_frame(const DevStream *__restrict__ st,
     __syncthreads();
 
     const int ndt = g.w * g.h, ntask = 24 * ndt;
+    if (bx * CODE_T >= ntask) return;                   /* a chunk past the frame's own rect (uniform) */
     const int task = bx * CODE_T + t;
     /* the frame's rect QP (k_dyn_rows: DynFrame.ep until k_dyn_epfix); below
      * QP_MIN the levels need 16 bits (wide) */
@@ -286,7 +287,7 @@ __device__ inline void code_frame(const DevStream *__restrict__ st,
     const QParams ql = qparams_rt(qpy), qc = qparams_rt(qp_chroma(qpy));
     const bool wide = qpy < QP_MIN;
     const size_t nb = (size_t)s * ld_fr + f;
-    const uint32_t *rw = rows + nb * (size_t)(32 * g.h);
+    const uint32_t *rw = rows + nb * (size_t)(32 * g.ld_h);   /* frames stride by the batch's h */
     const int w = st[s].w, h = st[s].h;
     const uint32_t ysz = (uint32_t)w * (uint32_t)h, csz = ysz / 4;
     const uint8_t *rb = refs + (size_t)s * g.ref_ld;
@@ -295,9 +296,10 @@ __device__ inline void code_frame(const DevStream *__restrict__ st,
     const uint8_t *fcb = fs + (size_t)256 * ndt, *fcr = fcb + (size_t)64 * ndt;
     const uint32_t m_rw = magic32((uint32_t)g.w);
     const size_t gs = df.rbsp_bytes;                    /* its record slot (k_dyn_rows) */
-    uint16_t *M = meta + gs * (size_t)(NPC * ndt);
-    uint2 *BL = blo + gs * (size_t)(NPC * ndt), *BH = bhi + gs * (size_t)(NPC * ndt);
-    uint4 *BW = bwd + gs * (size_t)(NPC * ndt);
+    const size_t gld = (size_t)NPC * g.ld_w * g.ld_h;   /* a record slot: the batch's rect */
+    uint16_t *M = meta + gs * gld;
+    uint2 *BL = blo + gs * gld, *BH = bhi + gs * gld;
+    uint4 *BW = bwd + gs * gld;
 
     const bool luma = task < 16 * ndt;
     const bool act = task < ntask;
@@ -852,7 +854,7 @@ __global__ __launch_bounds__(256) void k_dyn_rows(const DevStream *__restrict__ 
     const int w = c.w, h = c.h, a_end = (h - c.off) / 16;
     const uint32_t ysz = (uint32_t)w * (uint32_t)h, pic = ysz + ysz / 2;
     const WpTab T{wo, wv, h};
-    uint32_t *rw = rows + ((size_t)s * ld_fr + f) * (size_t)(32 * g.h);
+    uint32_t *rw = rows + ((size_t)s * ld_fr + f) * (size_t)(32 * g.ld_h);
     bool my_gen = false;
     for (int i = t; i < 32 * g.h; i += 256) {
         uint32_t e;
@@ -951,7 +953,8 @@ __global__ __launch_bounds__(GW) void k_dyn_static(const DevStream *__restrict__
     const int gi = (int)blockIdx.x >= nA ? (int)blockIdx.x + R.h : (int)blockIdx.x;
     const int ng = g.ngroups;
     if (gi >= ng) {
-        if (t == 0) gbits[nb * (size_t)g.ld_groups + gi] = 0u;
+        /* (a sized frame of many rows: gi may pass the frame's gbits row, which nobody reads there) */
+        if (t == 0 && gi < g.ld_groups) gbits[nb * (size_t)g.ld_groups + gi] = 0u;
         return;
     }
     const bool first = gi == 0, last = gi == ng - 1;
@@ -1645,6 +1648,12 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     }
     const size_t nb = (size_t)s * ld_fr + f;
     if (POS) dyn_frame_geom(gp, nb);
+    /* a frame sized on its own has h_f <= ld_h rows: the
+     * workgroups past them leave here, before any LDS or hand-off traffic --
+     * they publish nothing and nothing waits for them */
+    if (POS && r >= gp.h) return;
+    /* what strides between frames is the batch's size, the launch's */
+    const int ld_w = POS ? gp.ld_w : a.g.w, ld_h = POS ? gp.ld_h : a.g.h;
     constexpr bool general = GEN;
     constexpr int SR = DYN_STATIC_ROWS;
     /* the workgroup's slot, a uniform pointer (thread 0 writes: as thread
@@ -1680,7 +1689,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     bool fo_chroma = false;
     BlkPix nx;
     if (!general) {
-        const uint32_t *rtg = rows + nb * (size_t)(32 * g.h);
+        const uint32_t *rtg = rows + nb * (size_t)(32 * ld_h);
         const int k0 = kind_of(0);
         /* the row's entry t % 32 of that table, for its LDS copy (rt): issued
          * with the offsets' loads, one round trip for both */
@@ -1874,7 +1883,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
                 const int pcA = e < 4 ? 12 + e : (e < 6 ? 16 + e : 18 + e);
                 v |= (uint64_t)__builtin_popcount(mk[pcA]) << (5 * e);    /* the block's non-zero mask */
             }
-            lb_store(tcx + (nb * R.h + r) * (size_t)w + t, (uint64_t)(epoch & 0xffffffu) << 40 | v);
+            lb_store(tcx + (nb * ld_h + r) * (size_t)ld_w + t, (uint64_t)(epoch & 0xffffffu) << 40 | v);
         }
         /* class k's base: every wave scans the nine counts itself and reads
          * back its own stores (the same words from every wave): no barrier
@@ -2009,8 +2018,10 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         /* general path: records of k_dyn_code_general */
         const int q0 = r * w;
         const size_t gs = df.rbsp_bytes;                /* its record slot (k_dyn_rows) */
-        const uint16_t *M = a.meta + gs * (size_t)(NPC * ndt);
-        const uint2 *BL = a.blo + gs * (size_t)(NPC * ndt), *BH = a.bhi + gs * (size_t)(NPC * ndt);
+        /* a record slot: the batch's rect (POS: ndt is the frame's own) */
+        const size_t gld = POS ? (size_t)(NPC * ld_w * ld_h) : (size_t)(NPC * ndt);
+        const uint16_t *M = a.meta + gs * gld;
+        const uint2 *BL = a.blo + gs * gld, *BH = a.bhi + gs * gld;
         for (int i = t; i < npc; i += T) {
             const int k = div_npc(i), pc = i - k * NPC;
             const int rec = rec_of(q0 + k, pc, ndt);
@@ -2051,7 +2062,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
         for (int k = lane; k < w; k += 64) {
             uint64_t v = 0;
             if (r > 0) {
-                const unsigned long long *p = tcx + (nb * R.h + r - 1) * (size_t)w + k;
+                const unsigned long long *p = tcx + (nb * ld_h + r - 1) * (size_t)ld_w + k;
                 for (;;) {
                     v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if ((uint32_t)(v >> 40) == (epoch & 0xffffffu)) break;
@@ -2076,7 +2087,7 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     const bool wide = GEN && __builtin_amdgcn_readfirstlane((int)df.ep) < QP_MIN;
     auto ovf_wide = [&](int k, int pc) -> const uint4 * {
         if (!wide) return nullptr;
-        return a.bwd + (size_t)df.rbsp_bytes * (size_t)(NPC * ndt) + rec_of(r * w + k, pc, ndt);
+        return a.bwd + (size_t)df.rbsp_bytes * (POS ? (size_t)(NPC * ld_w * ld_h) : (size_t)(NPC * ndt)) + rec_of(r * w + k, pc, ndt);
     };
     __syncthreads();                                    /* records, top TotalCoeffs, waypoint table */
     if (stp && t == 0) stp[2] = __builtin_amdgcn_s_memrealtime();
@@ -2280,8 +2291,10 @@ __global__ __launch_bounds__(ROW_MAXT) __attribute__((amdgpu_waves_per_eu(SCROLL
     if (t == 0) gbits[nb * (size_t)row_arg(K5, g.ld_groups) + gi] = bits;
 
     /* ---- 5: bits -> the row's own row-stage words ------------------------ */
-    const bool wwin = row_wide_win(w);
-    uint32_t *const wb = wwin ? reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(rdyn) + row_wide_off(w)) : L.buf;
+    /* the launch's carve-up (the batch's width), not the frame's: the wide
+     * window lies where row_lds_bytes(ld_w) put it */
+    const bool wwin = row_wide_win(ld_w);
+    uint32_t *const wb = wwin ? reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(rdyn) + row_wide_off(ld_w)) : L.buf;
     const uint32_t GBW = wwin ? (uint32_t)ROW_GB_WIDE : (uint32_t)ROW_GB;
     /* rs_group_words of a rect row's group */
     uint32_t *out = rowstage + nb * rs_frame_words + ((uint64_t)nA * rs_static_words + (uint64_t)r * rs_row_words);
@@ -3944,6 +3957,7 @@ __global__ __launch_bounds__(256) void k_dyn_synth(uint8_t *__restrict__ src, Dy
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     const int f = blockIdx.y, s = blockIdx.z;
     dyn_frame_geom(g, (size_t)s * ld_fr + f);           /* the pattern is a function of picture coordinates */
+    /* (a sized frame: or_dyn_source's pattern for its own w_f x h_f rect, at the head of its slot) */
     const uint32_t npx = 384u * (uint32_t)g.w * (uint32_t)g.h;
     if (i >= npx) return;
     const uint32_t tt = (uint32_t)(t0 + f);
@@ -4076,7 +4090,7 @@ int dyn_launch_static(hipStream_t hs, int nframes, int S, DevStream *st, const N
                       const PlanPending *pend, DynFrame *dfr, int ld_fr, const DynGeom *g, const DynScratch *x)
 {
     if (nframes <= 0 || S <= 0) return 0;
-    hipLaunchKernelGGL(k_dyn_static, dim3(g->ld_groups - g->h, nframes, S), dim3(GW), 0, hs, st, nal, ld_nal,
+    hipLaunchKernelGGL(k_dyn_static, dim3(g->ld_static, nframes, S), dim3(GW), 0, hs, st, nal, ld_nal,
                        pend, dfr, ld_fr, *g, x->rowstage, x->gbits);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -4156,6 +4170,7 @@ void dyn_rowstage_geom(DynGeom *g, int mbw, int mbh, int moving)
         maxrows = mbh - g->h < SR ? mbh - g->h : SR;
         g->ld_groups = dyn_groups_max(g->h, mbh);
     }
+    if (moving > 1) maxrows = mbh - 1 < SR ? mbh - 1 : SR;     /* frames sized on their own: a one-row rect */
     auto words = [](uint64_t bits) { return (uint32_t)((((bits + 31) / 32) + 63) & ~(uint64_t)63); };
     /* + the group's EP-candidate record (EPC_ROW / EPC_STATIC words) at the slot end */
     g->rs_static_words = words((uint64_t)HDR_MAX + (uint64_t)maxrows * mbw * (HEAD_MAX + 1) + 64) + EPC_STATIC;
@@ -4166,6 +4181,15 @@ void dyn_rowstage_geom(DynGeom *g, int mbw, int mbh, int moving)
     g->rs_row_words = words((uint64_t)mbw * (HEAD_MAX + 1) + (uint64_t)g->w * SCROLL_DYN_ROW_KBITS + 64) + EPC_ROW;
     if (g->rs_row_words > g->rs_spill_words) g->rs_row_words = g->rs_spill_words;
     g->rs_frame_words = (uint64_t)(g->ld_groups - g->h) * g->rs_static_words + (uint64_t)g->h * g->rs_row_words;
+    g->ld_static = g->ld_groups - g->h;
+    if (moving > 1) {
+        /* every legal y0 and every 1 <= h_f <= h: a shorter
+         * rect has more static rows around it -- the largest of each */
+        const DynSizedMax m = dyn_sized_max(g->h, mbh, g->rs_static_words, g->rs_row_words);
+        g->ld_groups = m.groups;
+        g->ld_static = m.statics;
+        g->rs_frame_words = m.words;
+    }
 }
 
 /* EP positions kept per frame by the rows' path (the list buffer's stride / 4) */

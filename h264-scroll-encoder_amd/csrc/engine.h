@@ -125,6 +125,18 @@ typedef struct {
      * NULL: every frame at x0, y0.  A kernel that codes frame (s, f) replaces
      * x0, y0 and ngroups of its copy by the frame's (dyn_frame_geom) */
     const uint32_t *dpos;
+    /* scroll_batch_set_dyn_rect_size_at: the batch's rect
+     * size, which w and h above are everywhere but in a kernel's own copy --
+     * there dyn_frame_geom replaces w, h by the frame's w_f <= ld_w, h_f <=
+     * ld_h.  Everything that strides between frames (the rows table, the
+     * hand-off granules, the mask map) or sizes a launch or an allocation
+     * reads these two.  A table entry carries ld_w - w_f in bits 8-15 and
+     * ld_h - h_f in bits 24-31 where pos_mask is 0xff (pictures of at most 256
+     * MBs each way: origins fit a byte); 0xffff: origins take 16 bits, no
+     * frame has a size of its own */
+    int32_t ld_w, ld_h;
+    uint32_t pos_mask;
+    int32_t ld_static;              /* k_dyn_static's grid: the most static row groups of any frame */
 } DynGeom;
 #define DYN_POS_NONE 0xffffffffu
 

@@ -19,7 +19,12 @@
  * the rect as I420) is overwritten by their prediction; part[(s ld_fr + f)
  * g.h + r][2]: the Cb / Cr squared error of rect row r's MBs not kept;
  * res[s ld_fr + f]: the record.  Frames whose dfr[].nal < 0: zero entries,
- * a NOFRAME record, nothing else touched. */
+ * a NOFRAME record, nothing else touched.
+ * A frame sized on its own (g.dpos) is, inside its own
+ * blocks, a batch whose rect is w_f x h_f: its map block starts at (s ld_fr
+ * + f) g.ld_h g.ld_w pairs and holds [my w_f + mx], its part rows start at
+ * (s ld_fr + f) g.ld_h; the rest of either block is not written.  g.w, g.h
+ * here are the batch's (= g.ld_w, g.ld_h): they size the launch. */
 typedef struct {
     const DevStream *st;
     const NalDesc *nal;

@@ -86,10 +86,10 @@ __device__ inline uint32_t quad_sum(uint32_t v)
  * whether some chroma row of it runs through a half-pel chain.  Everything
  * here is uniform over the wave. */
 template <bool GEN>
-__device__ inline bool row_table(const MaskJob &j, size_t nb, int s, int r, ReconLds &L)
+__device__ inline bool row_table(const MaskJob &j, const DynGeom &g, size_t nb, int s, int r, ReconLds &L)
 {
-    const int h = j.g.h;
-    const uint32_t *rw = j.rows + nb * (size_t)(32 * h);
+    const int h = g.h;                                  /* the frame's own; frames stride by the batch's */
+    const uint32_t *rw = j.rows + nb * (size_t)(32 * g.ld_h);
 #pragma unroll
     for (int i = 0; i < 16; ++i) L.rt[i] = rw[16 * r + i];
 #pragma unroll
@@ -181,17 +181,19 @@ __global__ __launch_bounds__(MK_T) void k_dyn_mask_diff(MaskArgs a)
     }
     const size_t nb = (size_t)s * j.ld_fr + f;
     const uint32_t mx = 16u * sp + mbl;
-    const bool on = mx < (uint32_t)j.g.w;               /* a partial last span */
-    uint2 *mp = reinterpret_cast<uint2 *>(j.map) + (nb * (size_t)j.g.h + r) * (size_t)j.g.w + mx;
+    DynGeom g = j.g;
+    dyn_frame_geom(g, nb);                              /* RowPred's origin and the rect's size: the frame's own */
+    if (r >= (uint32_t)g.h) return;                     /* past the rows of a frame sized on its own */
+    const bool on = mx < (uint32_t)g.w;                 /* a partial last span, or past the frame's own columns */
+    /* the frame's block of the map keeps the batch's stride; inside it the map is the frame's own w_f x h_f */
+    uint2 *mp = reinterpret_cast<uint2 *>(j.map) + nb * (size_t)g.ld_h * (size_t)g.ld_w + (size_t)r * (size_t)g.w + mx;
     const DynFrame df = j.dfr[nb];
     if (df.nal < 0) {                                   /* no dynamic NAL: zero entries */
         if (!GEN && on && q == 0u) *mp = make_uint2(0u, 0u);
         return;
     }
-    DynGeom g = j.g;
-    dyn_frame_geom(g, nb);                              /* RowPred's origin: the frame's own */
     ReconLds L;
-    if (row_table<GEN>(j, nb, (int)s, (int)r, L) != GEN) return;
+    if (row_table<GEN>(j, g, nb, (int)s, (int)r, L) != GEN) return;
     const uint8_t *rb = j.refs + (size_t)s * g.ref_ld;
     const RowPred<GEN> P{L, rb, (uint32_t)g.pw * (uint32_t)g.ph / 4, g.x0, g.y0 + (int)r, j.st + s,
                          j.nal + (size_t)s * j.ld_nal + df.nal};
@@ -233,13 +235,14 @@ __global__ __launch_bounds__(MK_T) void k_dyn_mask_fill(MaskArgs a)
     if (df.nal < 0) return;                             /* no dynamic NAL: the source stays */
     DynGeom g = j.g;
     dyn_frame_geom(g, nb);
+    if (r >= (uint32_t)g.h) return;                     /* past the rows of a frame sized on its own */
     ReconLds L;
-    if (row_table<GEN>(j, nb, (int)s, (int)r, L) != GEN) return;
+    if (row_table<GEN>(j, g, nb, (int)s, (int)r, L) != GEN) return;
     const uint8_t *rb = j.refs + (size_t)s * g.ref_ld;
     const RowPred<GEN> P{L, rb, (uint32_t)g.pw * (uint32_t)g.ph / 4, g.x0, g.y0 + (int)r, j.st + s,
                          j.nal + (size_t)s * j.ld_nal + df.nal};
     uint8_t *fs = j.src + (size_t)s * g.src_ld + (size_t)f * g.src_fr;
-    const uint32_t *fm = j.map + nb * (size_t)g.h * (size_t)g.w * 2u;
+    const uint32_t *fm = j.map + nb * (size_t)g.ld_h * (size_t)g.ld_w * 2u;
     const uint32_t w = (uint32_t)g.w, h = (uint32_t)g.h;
     uint32_t e = 0u;                                    /* this lane's plane (q >> 1): squared error dropped */
     for (uint32_t sp = wave; sp < a.nsp; sp += MK_WAVES) {
@@ -272,7 +275,7 @@ __global__ __launch_bounds__(MK_T) void k_dyn_mask_fill(MaskArgs a)
         unsigned long long v = 0;
 #pragma unroll
         for (uint32_t k = 0; k < MK_WAVES; ++k) v += red[k][threadIdx.x];
-        j.part[(nb * (size_t)g.h + r) * 2u + threadIdx.x] = v;
+        j.part[(nb * (size_t)g.ld_h + r) * 2u + threadIdx.x] = v;
     }
 }
 
@@ -287,14 +290,16 @@ __global__ __launch_bounds__(MK_T) void k_dyn_mask_rec(MaskArgs a)
         if (t == 0u) j.res[nb] = noframe();
         return;
     }
-    const uint32_t w = (uint32_t)j.g.w, h = (uint32_t)j.g.h, nmb = w * h;
-    uint32_t *fm = j.map + nb * (size_t)nmb * 2u;
+    DynGeom g = j.g;
+    dyn_frame_geom(g, nb);                              /* the frame's own w_f x h_f MBs */
+    const uint32_t w = (uint32_t)g.w, h = (uint32_t)g.h, nmb = w * h;
+    uint32_t *fm = j.map + nb * (size_t)g.ld_h * (size_t)g.ld_w * 2u;
     Acc acc = acc_init();
     /* the KEPT bit goes into words whose other 31 bits never change, and a
      * neighbour's read masks it off: what another thread sees of this
      * thread's store does not matter */
     for (uint32_t i = t; i < nmb; i += MK_T) fm[2u * i + 1u] = acc_mb(acc, fm, w, h, i % w, i / w, j.rule);
-    const unsigned long long *pr = j.part + nb * (size_t)h * 2u;
+    const unsigned long long *pr = j.part + nb * (size_t)g.ld_h * 2u;
     for (uint32_t r = t; r < h; r += MK_T) {
         acc.drop[1] += pr[2u * r];
         acc.drop[2] += pr[2u * r + 1u];

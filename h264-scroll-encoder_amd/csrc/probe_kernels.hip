@@ -118,10 +118,16 @@ __global__ __launch_bounds__(PB_T) void k_dyn_probe(const DevStream *__restrict_
     const DynFrame df = dfr[nb];
     if (df.nal < 0) return;                              /* no dynamic NAL in this frame */
     dyn_frame_geom(g, nb);                               /* RowPred's origin, avl / avt: the frame's own */
+    if (r >= g.h) {
+        /* past the rows of a frame sized on its own: nothing to count, but
+         * done[] stays the batch's h for every frame (once: GEN walks only the listed frames) */
+        if (!GEN && t == 0) atomicAdd(&done[nb], 1u);
+        return;
+    }
     const bool above = r > 0;                            /* the row above is a rect row */
     if (t < 64) {
         const int i = t & 31, rr = t < 32 ? r : (above ? r - 1 : r);
-        const uint32_t e = rows[nb * (size_t)(32 * g.h) +
+        const uint32_t e = rows[nb * (size_t)(32 * g.ld_h) +
                                 (i < 16 ? 16 * rr + i : 16 * g.h + (i < 24 ? 8 * rr + i - 16 : 8 * g.h + 8 * rr + i - 24))];
         if (t < 32) L.cur.rt[i] = e;
         else L.abv.rt[i] = e;

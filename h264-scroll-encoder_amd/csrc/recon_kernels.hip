@@ -67,8 +67,9 @@ __global__ __launch_bounds__(RC_T) void k_dyn_recon(const DevStream *__restrict_
     const DynFrame df = dfr[nb];
     if (df.nal < 0) return;                              /* no dynamic NAL in this frame */
     dyn_frame_geom(g, nb);                               /* RowPred's origin: the frame's own */
+    if (r >= g.h) return;                                /* past the rows of a frame sized on its own */
     if (t < 32)
-        L.rt[t] = rows[nb * (size_t)(32 * g.h) +
+        L.rt[t] = rows[nb * (size_t)(32 * g.ld_h) +
                        (t < 16 ? 16 * r + t : 16 * g.h + (t < 24 ? 8 * r + t - 16 : 8 * g.h + 8 * r + t - 24))];
     else if (t >= 64 && t < 72) {
         L.wo[t - 64] = pend[s].wo[t - 64];

@@ -166,7 +166,7 @@ class ScrollDynDamage(ctypes.Structure):
 
 class ScrollDynLocate(ctypes.Structure):
     _fields_ = [("mb_sse", ctypes.c_uint32), ("margin", ctypes.c_uint32), ("apply", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32)]
+                ("size", ctypes.c_uint32)]
 
 
 SCROLL_DYN_MASK_OK, SCROLL_DYN_MASK_NOFRAME = 0, 1
@@ -243,6 +243,7 @@ def _load():
         "scroll_batch_set_dyn_source": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_int]),
         "scroll_batch_set_dyn_rect_at": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
         "scroll_batch_set_dyn_rect_moving": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+        "scroll_batch_set_dyn_rect_size_at": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
         "scroll_batch_set_fallback": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
         "scroll_batch_fallback_frame": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                        ctypes.POINTER(ctypes.c_int)]),
@@ -772,6 +773,15 @@ class Batch:
         dynamic rect; set_dyn_rect drops the flag."""
         self._chk(lib.scroll_batch_set_dyn_rect_moving(self.h, 1 if on else 0), "set_dyn_rect_moving")
 
+    def set_dyn_rect_size_at(self, s, f, w, h):
+        """Frame f of stream s codes a rect of w x h MBs (1 <= w, h <= the
+        size of set_dyn_rect) at the frame's own origin; its source, dyn_recon
+        and mask-map blocks are then laid out as a w x h rect's, at the head of
+        the frame's slot.  Needs set_dyn_rect_moving; entry f holds for frame f
+        of every following compose; set_dyn_rect and clear_hints reset it.
+        Not followed under UI hints (compose returns SCROLL_ERR_CONFIG)."""
+        self._chk(lib.scroll_batch_set_dyn_rect_size_at(self.h, s, f, w, h), "set_dyn_rect_size_at")
+
     def set_fallback(self, on=True):
         """the conventional-encode fallback (scroll_batch_set_fallback): frames
         whose hints name a reference they lack are coded as whole P frames"""
@@ -827,7 +837,8 @@ class Batch:
 
     # ---- the rect located from the surfaces ----
     def dyn_locate(self, ptr, nframes, pitch, frame_stride, stream_stride=0, fmt=SCROLL_SURF_RGBA,
-                   matrix=SCROLL_SURF_BT601, full_range=False, mb_sse=0, margin=0, apply=True, stream=None):
+                   matrix=SCROLL_SURF_BT601, full_range=False, mb_sse=0, margin=0, apply=True, stream=None,
+                   size=False):
         """frames 0 .. nframes - 1 of every stream: the per-MB squared luma
         difference between the whole-picture surfaces (dyn_source_from_surfaces'
         layout) and the scroll prediction at set_offsets' offsets, and from it
@@ -835,9 +846,12 @@ class Batch:
         when its sum exceeds mb_sse, the damaged MBs' box grows by margin MBs.
         apply: the positions become the frames' (needs set_dyn_rect_moving);
         dyn_source_from_surfaces, dyn_probe and compose on the same `stream`
-        then follow them without a host step.  Asynchronous on `stream`"""
+        then follow them without a host step.  size (with apply): the rect is
+        also sized per frame, from its origin to the box's end or the batch
+        size (set_dyn_rect_size_at's contract); the record's `reserved` then
+        holds (w_f - 1) | (h_f - 1) << 8.  Asynchronous on `stream`"""
         sf = ScrollSurfaces(ptr, pitch, frame_stride, stream_stride, fmt, matrix, 1 if full_range else 0, 0)
-        rule = ScrollDynLocate(int(mb_sse), int(margin), 1 if apply else 0, 0)
+        rule = ScrollDynLocate(int(mb_sse), int(margin), 1 if apply else 0, int(size))
         self._chk(lib.scroll_batch_dyn_locate(self.h, nframes, ctypes.byref(sf), ctypes.byref(rule), stream),
                   "dyn_locate")
 

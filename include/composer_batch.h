@@ -247,6 +247,35 @@ int scroll_batch_set_dyn_rect_at(ScrollBatch *b, int s, int f, int x0, int y0);
  *       hints-only.  Off (the default): nothing changes -- a moved position
  *       without hints is refused at compose time. */
 int scroll_batch_set_dyn_rect_moving(ScrollBatch *b, int on);
+/* The plain rect sized per stream and per frame, on the same path:
+ *   scroll_batch_set_dyn_rect_size_at(b, s, f, w_f, h_f)   frame f of stream s
+ *       codes a rect of w_f x h_f MBs at the frame's own origin (the
+ *       batch's, set_dyn_rect_at's or a locate's), 1 <= w_f <= w, 1 <= h_f <=
+ *       h of set_dyn_rect (SCROLL_ERR_ARG otherwise); (w, h) restores the
+ *       batch size.  Frame f is then, byte for byte, the NAL of a batch whose
+ *       rect is w_f x h_f at that origin.  Needs set_dyn_rect_moving
+ *       (SCROLL_ERR_CONFIG without it) and a picture of at most 256 x 256
+ *       MBs (SCROLL_ERR_CONFIG).  Entry f holds for frame f of every
+ *       following compose; set_dyn_rect and clear_hints reset sizes together
+ *       with positions.  Origins stay legal by the batch size (x0 + w <= mbw,
+ *       y0 + h <= mbh), so a sized rect never leaves the picture; a frame
+ *       without a rect stays x0 = -1 (there is no size 0).  The first call
+ *       sizes the row stage for every (y0, h_f), once; no later one allocates.
+ *   Layout: a sized frame is, inside its own slots, a batch whose rect is
+ *       w_f x h_f.  Its source block (set_dyn_source, _dyn_source_device,
+ *       _from_surfaces, _synth) is luma 16 h_f rows of 16 w_f bytes, then Cb
+ *       and Cr at 8 w_f x 8 h_f, at the start of the frame's slot; the same
+ *       holds for its scroll_batch_dyn_recon block and its mask-map block
+ *       (w_f x h_f pairs).  Slots keep the batch's strides (384 w h bytes a
+ *       frame); the rest of a slot is neither read nor written.
+ *   The per-frame QP table, the reconstruction and dyn_sse, the probe, the
+ *       pick, the mask, dyn_source_synth and dyn_source_from_surfaces follow
+ *       the sizes; scroll_batch_dyn_locate places them with size = 1.  With
+ *       UI hints set, a compose (its reconstruction included) or a hinted
+ *       probe returns SCROLL_ERR_CONFIG while any frame has a size of its
+ *       own.  Never called: nothing changes -- no launch, no allocation, no
+ *       byte. */
+int scroll_batch_set_dyn_rect_size_at(ScrollBatch *b, int s, int f, int w, int h);
 /* The conventional-encode fallback (docs/MASTER_DESIGN.md:220: "if hints
  * missing/inconsistent -> full conventional encode"), opt-in:
  *   scroll_batch_set_fallback(b, 1)   with UI hints and a dynamic rect that
@@ -869,7 +898,17 @@ float scroll_batch_surface_ms(ScrollBatch *b);   /* with enable_timing; -1 witho
  *       frame, the dry pass's plan) are allocated by the first call and go
  *       with the rect; a batch that never calls it gains no launch,
  *       allocation or changed byte.
- *   scroll_batch_dyn_locate_result / _damage_map   one frame's record / its
+ *       rule.size (the rule's fourth word, which was reserved and 0): 0 as
+ *       above, byte for byte, the records included.  1, with apply = 1: the
+ *       rect keeps the placed origin and is also sized per frame
+ *       (scroll_batch_set_dyn_rect_size_at's contract), w_f = min(bx1, x0 +
+ *       w) - x0, h_f = min(by1, y0 + h) - y0: a FIT rect covers exactly
+ *       origin-to-box-end, an OVER rect is the batch size where it is over.
+ *       sse_out is then summed outside the sized rect and the record's
+ *       reserved holds (w_f - 1) | (h_f - 1) << 8 on FIT / OVER, else 0.
+ *       size > 1, or size = 1 without apply, is SCROLL_ERR_ARG; size = 1
+ *       needs what set_dyn_rect_size_at needs (SCROLL_ERR_CONFIG).
+ *   scroll_batch_dyn_locate_result / _damage_map  one frame's record / its
  *       mbw * mbh map entries, row by row (synchronising; SCROLL_ERR_CONFIG
  *       before the first locate, SCROLL_ERR_ARG outside the last one)
  *   scroll_batch_dyn_locate_device / _damage_map_device   the device arrays,
@@ -888,7 +927,7 @@ typedef struct {
     uint32_t n_mb, max_sse;
     uint64_t sse_all, sse_out;
 } ScrollDynDamage;                 /* 40 bytes */
-typedef struct { uint32_t mb_sse, margin, apply, reserved; } ScrollDynLocate;
+typedef struct { uint32_t mb_sse, margin, apply, size; } ScrollDynLocate;
 int scroll_batch_dyn_locate(ScrollBatch *b, int nframes, const ScrollSurfaces *surf,
                             const ScrollDynLocate *rule, void *hip_stream);
 int scroll_batch_dyn_locate_result(ScrollBatch *b, int s, int f, ScrollDynDamage *out);   /* synchronising */
