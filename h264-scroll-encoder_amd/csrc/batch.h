@@ -9,6 +9,7 @@
  *   batch_surface.hip pixels from RGBA / BGRA surfaces: the rect's source, I420 pictures, device references
  *   batch_damage.hip  the rect located from the surfaces: damage map, placement, the positions' device ownership
  *   batch_mask.hip    the rect's per-MB source mask: difference map, keep decision, fill
+ *   batch_detect.hip  each frame's scroll offset detected from the surfaces: signatures, scores, the choice
  *   batch_dropin.hip  the synchronous drop-in helpers of engine.h
  * Nothing here enters the library's dynamic symbol table.
  */
@@ -167,6 +168,20 @@ struct ScrollBatch {
         hipEvent_t ev[4] = {};          /* timing: the call's start, around k_dyn_mask_diff, its end (created on first use) */
         int timed = 0;
     } mk;
+    /* each frame's scroll offset detected from the surfaces
+     * (scroll_batch_detect_offsets, batch_detect.hip, detect_kernels.hip):
+     * both signature arrays, the scores and the records; nothing here exists
+     * before the first detect, everything goes with the rect */
+    struct Detect {
+        uint16_t *sig_s = nullptr;      /* [max_streams * max_frames][ph][nseg] (the call's nuse of them) */
+        uint16_t *sig_r = nullptr;      /* [max_streams][nseg][2 ph] */
+        uint32_t *scores = nullptr;     /* [max_streams * max_frames][ph + 1] */
+        ScrollOffsetFound *res = nullptr;   /* [max_streams * max_frames] */
+        int nframes = -1, nstreams = 0; /* the last detect; nframes -1: none */
+        hipEvent_t fin = nullptr;       /* recorded after the last detect's launches */
+        hipEvent_t ev[5] = {};          /* timing: the call's start, around k_det_surf, after k_det_score, its end (created on first use) */
+        int timed = 0;
+    } dt;
     /* UI hints: staged like the dynamic rect (shares
      * d_dfr, d_stage and geo.slot_bytes; the two are exclusive) */
     int hint_on = 0;
@@ -352,6 +367,9 @@ int dyn_pos_refresh(ScrollBatch *b);
 
 /* ---- batch_mask.hip ---- */
 void mask_release(ScrollBatch *b);
+
+/* ---- batch_detect.hip ---- */
+void detect_release(ScrollBatch *b);
 
 }  // namespace batch
 }  // namespace scroll

@@ -543,6 +543,7 @@ void scroll_batch_destroy(ScrollBatch *b)
     probe_release(b);
     locate_release(b);
     mask_release(b);
+    detect_release(b);
     (void)hipFree(b->dx.qpf);
     rate_release(b);
     surface_release(b, true);

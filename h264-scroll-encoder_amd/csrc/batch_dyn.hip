@@ -51,6 +51,7 @@ void dyn_release(ScrollBatch *b)
     probe_release(b);
     locate_release(b);                 /* the locate's buffers, and the device's ownership of the positions */
     mask_release(b);
+    detect_release(b);
     if (!b->hint_on) {                 /* else they are the hint path's */
         (void)hipFree(b->d_dfr);
         (void)hipFree(b->d_stage);

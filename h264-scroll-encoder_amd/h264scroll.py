@@ -184,6 +184,22 @@ class ScrollDynMask(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("sse_drop", ctypes.c_uint64 * 3)]
 
 
+SCROLL_DET_LOW, SCROLL_DET_FOUND, SCROLL_DET_TIED = 0, 1, 2
+
+
+class ScrollOffsetFound(ctypes.Structure):
+    """include/composer_batch.h: one frame's record of scroll_batch_detect_offsets"""
+    _fields_ = [("off", ctypes.c_int32), ("centre", ctypes.c_int32), ("score", ctypes.c_uint32),
+                ("second", ctypes.c_uint32), ("second_off", ctypes.c_int32), ("n_sig", ctypes.c_uint32),
+                ("lo", ctypes.c_uint16), ("hi", ctypes.c_uint16), ("status", ctypes.c_uint16),
+                ("reserved", ctypes.c_uint16)]
+
+
+class ScrollDetect(ctypes.Structure):
+    _fields_ = [("radius", ctypes.c_uint32), ("seg_step", ctypes.c_uint32), ("min_match", ctypes.c_uint32),
+                ("apply", ctypes.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} not built: run `make -C h264-scroll-encoder_amd` "
@@ -353,6 +369,18 @@ def _load():
                                                                P(ctypes.c_size_t)]),
         "scroll_batch_dyn_mask_ms": (ctypes.c_float, [ctypes.c_void_p]),
         "scroll_batch_dyn_mask_kernel_ms": (ctypes.c_float, [ctypes.c_void_p]),
+        "scroll_batch_detect_offsets": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, P(ScrollSurfaces),
+                                                       P(ScrollDetect), ctypes.c_void_p]),
+        "scroll_batch_detect_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                      P(ScrollOffsetFound)]),
+        "scroll_batch_detect_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t)]),
+        "scroll_batch_detect_scores": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                      P(ctypes.c_uint32)]),
+        "scroll_batch_detect_scores_device": (ctypes.c_void_p, [ctypes.c_void_p, P(ctypes.c_size_t),
+                                                                P(ctypes.c_size_t)]),
+        "scroll_batch_detect_ms": (ctypes.c_float, [ctypes.c_void_p]),
+        "scroll_batch_detect_kernel_ms": (ctypes.c_float, [ctypes.c_void_p]),
+        "scroll_batch_detect_score_ms": (ctypes.c_float, [ctypes.c_void_p]),
         "composer_batch_write_scroll_frames": (ctypes.c_int, [P(P(Composer)), P(ctypes.c_int),
                                                               ctypes.c_int, ctypes.c_int]),
         "composer_flush": (ctypes.c_int, [P(Composer)]),
@@ -953,6 +981,67 @@ class Batch:
         (kernel: of k_dyn_mask_diff alone); -1 without"""
         return (lib.scroll_batch_dyn_mask_kernel_ms if kernel else lib.scroll_batch_dyn_mask_ms)(self.h)
 
+    # ---- each frame's scroll offset detected from the surfaces ----
+    def detect_offsets(self, ptr, nframes, pitch, frame_stride, stream_stride=0, fmt=SCROLL_SURF_RGBA,
+                       matrix=SCROLL_SURF_BT601, full_range=False, radius=16, seg_step=1, min_match=1, apply=True,
+                       stream=None):
+        """frames 0 .. nframes - 1 of every stream: the scroll offset at which
+        the whole-picture surface (dyn_source_from_surfaces' layout) agrees
+        best with the stacked reference pictures, searched within `radius` of
+        the estimate the offsets hold (set_offsets; radius >= the picture's
+        height: every offset), over every seg_step-th segment of 64 columns
+        (scroll_batch_detect_offsets).  A frame is FOUND when its best score
+        reaches min_match and beats every other candidate's.  apply: FOUND
+        frames' offsets replace the estimates on the device, where dyn_locate,
+        dyn_probe and compose on the same `stream` read them; synchronise that
+        stream before the next set_offsets.  Asynchronous on `stream`"""
+        sf = ScrollSurfaces(ptr, pitch, frame_stride, stream_stride, fmt, matrix, 1 if full_range else 0, 0)
+        rule = ScrollDetect(int(radius), int(seg_step), int(min_match), 1 if apply else 0)
+        self._chk(lib.scroll_batch_detect_offsets(self.h, nframes, ctypes.byref(sf), ctypes.byref(rule), stream),
+                  "detect_offsets")
+
+    def detect_result(self, nframes):
+        """the last detect_offsets' records: a numpy structured array
+        [S][nframes] with ScrollOffsetFound's fields (status SCROLL_DET_*).
+        Synchronises"""
+        import numpy as np
+        out = np.zeros((self.num_streams, nframes), dtype=_detect_dtype())
+        r = ScrollOffsetFound()
+        for s in range(out.shape[0]):
+            for f in range(nframes):
+                self._chk(lib.scroll_batch_detect_result(self.h, s, f, ctypes.byref(r)), "detect_result")
+                out[s, f] = tuple(getattr(r, n) for n in out.dtype.names)
+        return out
+
+    def detect_scores(self, s, f):
+        """the last detect_offsets' scores of one frame: uint32 [ph + 1],
+        score(o) at index o inside the window, 0xFFFFFFFF outside.  Synchronises"""
+        import numpy as np
+        out = np.zeros(self.config(0).height + 1, dtype=np.uint32)
+        self._chk(lib.scroll_batch_detect_scores(self.h, s, f, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
+                  "detect_scores")
+        return out
+
+    def detect_device(self):
+        """(device pointer, stream stride in bytes) of the records, ScrollOffsetFound [stream][frame]"""
+        ls = ctypes.c_size_t()
+        p = lib.scroll_batch_detect_device(self.h, ctypes.byref(ls))
+        return p, ls.value
+
+    def detect_scores_device(self):
+        """(device pointer, stream stride, frame stride in bytes) of the scores, uint32 [stream][frame][ph + 1]"""
+        ls, lf = ctypes.c_size_t(), ctypes.c_size_t()
+        p = lib.scroll_batch_detect_scores_device(self.h, ctypes.byref(ls), ctypes.byref(lf))
+        return p, ls.value, lf.value
+
+    def detect_ms(self, kernel=False, score=False):
+        """with enable_timing: HIP-event ms of the last detect_offsets'
+        launches (kernel: of k_det_surf alone; score: of k_det_score and
+        k_det_pick); -1 without"""
+        f = lib.scroll_batch_detect_kernel_ms if kernel else lib.scroll_batch_detect_score_ms if score else \
+            lib.scroll_batch_detect_ms
+        return f(self.h)
+
     def dyn_source_synth(self, nframes, stream_base=0, t0=0):
         self._chk(lib.scroll_batch_dyn_source_synth(self.h, nframes, stream_base, t0),
                   "dyn_source_synth")
@@ -1158,6 +1247,13 @@ def _damage_dtype():
     return np.dtype([("x0", np.int16), ("y0", np.int16), ("bx0", np.uint16), ("by0", np.uint16), ("bx1", np.uint16),
                      ("by1", np.uint16), ("status", np.uint16), ("reserved", np.uint16), ("n_mb", np.uint32),
                      ("max_sse", np.uint32), ("sse_all", np.uint64), ("sse_out", np.uint64)])
+
+
+def _detect_dtype():
+    import numpy as np
+    return np.dtype([("off", np.int32), ("centre", np.int32), ("score", np.uint32), ("second", np.uint32),
+                     ("second_off", np.int32), ("n_sig", np.uint32), ("lo", np.uint16), ("hi", np.uint16),
+                     ("status", np.uint16), ("reserved", np.uint16)])
 
 
 def _mask_dtype():

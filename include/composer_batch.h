@@ -1015,6 +1015,88 @@ const uint32_t *scroll_batch_dyn_mask_map_device(ScrollBatch *b, size_t *stream_
 float scroll_batch_dyn_mask_ms(ScrollBatch *b);     /* with enable_timing; -1 without */
 float scroll_batch_dyn_mask_kernel_ms(ScrollBatch *b);     /* the same for k_dyn_mask_diff alone */
 
+/* ---- each frame's scroll offset detected from the surfaces ----
+ * The one per-frame input that still comes from the renderer as a hint is the
+ * scroll offset.  The device holds both sides of the question -- the surfaces
+ * and reference pictures A and B, whose stacked rows R[r] (row r of A for r <
+ * ph, row r - ph of B otherwise) are what a scroll at offset o shows: picture
+ * row Y displays R[Y + o] -- so the offset is a search over at most ph + 1
+ * vertical displacements (csrc/detect_device.h).  Pure integer:
+ *   segments   64 columns wide, nseg = ceil(pw / 64) (the last one 16, 32 or
+ *              48 wide); used: 0, seg_step, 2 seg_step, ... < nseg (nuse).
+ *   signatures sigR[r][c] = the sum of R[r][x] over segment c; sigS[Y][c] =
+ *              the sum of the luma rule above over segment c of surface row Y.
+ *   window     c0 = clamp(offsets[s][f], 0, ph) is the caller's estimate (the
+ *              last known offset, say); lo = max(c0 - radius, 0), hi =
+ *              min(c0 + radius, ph); radius >= ph searches every offset.
+ *   score(o)   = #{ (Y, used c) : sigS[Y][c] == sigR[Y + o][c] }, Y < ph, out
+ *              of n_sig = ph nuse.  Exact agreements are counted, differences
+ *              are not summed: the rows the dynamic rect covers do not vote.
+ *   choice     off = the candidate largest under (score descending, |o - c0|
+ *              ascending, o ascending); second / second_off = the score and
+ *              offset of the largest other candidate under the same key (0
+ *              and -1 without one).
+ *   SCROLL_DET_LOW    score < min_match
+ *   SCROLL_DET_FOUND  score >= min_match and score > second
+ *   SCROLL_DET_TIED   score >= min_match and score == second: a flat or
+ *                     periodic page, the offsets cannot be told apart
+ * The tearing of the MB row that straddles A and B and the waypoint chain are
+ * not modelled: the locate that follows at the detected offset counts them as
+ * damage.  Luma only, vertical full-pel motion only.
+ *
+ *   scroll_batch_detect_offsets(b, nframes, &surf, &rule, hip_stream)
+ *       frames 0 .. nframes - 1 of every stream: the records, the scores and,
+ *       with rule.apply = 1, offsets[s][f] = off for FOUND frames only (LOW
+ *       and TIED frames and entries from nframes on keep their values), in the
+ *       device array scroll_batch_offsets_device, which the locate, the probe
+ *       and the compose that follow read.  k_det_refs, k_det_surf,
+ *       k_det_score, k_det_pick; it reads no stream state, so it works with
+ *       UI hints set and in experiment mode.  Asynchronous on hip_stream (0 =
+ *       the batch's own), which must be the stream of the locate, the
+ *       conversion and the compose that follow: a tick becomes detect ->
+ *       locate -> ..., the estimate left in the offsets by
+ *       scroll_batch_set_offsets or by device code.  scroll_batch_set_offsets
+ *       copies synchronously on another stream: after a detect with apply,
+ *       synchronise hip_stream before calling it.
+ *       SCROLL_ERR_CONFIG without a dynamic rect with reference pictures;
+ *       SCROLL_ERR_ARG for a NULL rule, nframes outside 0..max_frames,
+ *       seg_step 0 or above nseg, apply > 1, cropped = 1, the surface checks
+ *       above and more than 2^35 pixels in one call.  A refused call writes
+ *       nothing.  Records, scores and both signature arrays (recomputed by
+ *       every call) are allocated by the first call and go with the rect; a
+ *       batch that never calls it gains no launch, allocation or changed byte.
+ *   scroll_batch_detect_result / _scores   one frame's record / its ph + 1
+ *       scores: score(o) at index o for lo <= o <= hi, 0xFFFFFFFF elsewhere
+ *       (synchronising; SCROLL_ERR_CONFIG before the first detect,
+ *       SCROLL_ERR_ARG outside the last one)
+ *   scroll_batch_detect_device / _scores_device   the device arrays,
+ *       [stream][frame] records and [stream][frame][ph + 1] uint32 (strides in
+ *       bytes); NULL before the first detect
+ *   scroll_batch_detect_ms / _kernel_ms   with scroll_batch_enable_timing:
+ *       HIP-event ms of the last detect's launches / of k_det_surf alone; -1
+ *       without. */
+#define SCROLL_DET_LOW   0
+#define SCROLL_DET_FOUND 1
+#define SCROLL_DET_TIED  2
+typedef struct {
+    int32_t  off, centre;          /* the chosen offset; c0, the clamped estimate */
+    uint32_t score, second;
+    int32_t  second_off;           /* -1: no other candidate */
+    uint32_t n_sig;                /* ph nuse: what score is out of */
+    uint16_t lo, hi;               /* the window searched */
+    uint16_t status, reserved;     /* SCROLL_DET_* */
+} ScrollOffsetFound;               /* 32 bytes */
+typedef struct { uint32_t radius, seg_step, min_match, apply; } ScrollDetect;
+int scroll_batch_detect_offsets(ScrollBatch *b, int nframes, const ScrollSurfaces *surf,
+                                const ScrollDetect *rule, void *hip_stream);
+int scroll_batch_detect_result(ScrollBatch *b, int s, int f, ScrollOffsetFound *out);     /* synchronising */
+const ScrollOffsetFound *scroll_batch_detect_device(ScrollBatch *b, size_t *stream_stride);
+int scroll_batch_detect_scores(ScrollBatch *b, int s, int f, uint32_t *dst);              /* ph + 1, synchronising */
+const uint32_t *scroll_batch_detect_scores_device(ScrollBatch *b, size_t *stream_stride, size_t *frame_stride);
+float scroll_batch_detect_ms(ScrollBatch *b);          /* with enable_timing; -1 without */
+float scroll_batch_detect_kernel_ms(ScrollBatch *b);   /* the same for k_det_surf alone */
+float scroll_batch_detect_score_ms(ScrollBatch *b);    /* the same for k_det_score + k_det_pick */
+
 /* Composer-level batch: offsets[i] composed on cs[i], i < n, in
  * order; Composers may repeat.  Output lands in each Composer's buffer before
  * return (equivalent to n composer_write_scroll_frame calls + a flush). */
