@@ -2,6 +2,7 @@
  * batch.h -- internal to the host-side batch engine behind
  * include/composer_batch.h: the batch's state and what its files share.
  *   batch_core.hip    create / destroy, streams, compose, sync, output, timing
+ *   batch_pass.hip    what the side passes share: the last-run record, the dry plan, the prediction rows
  *   batch_dyn.hip     the dynamic rect, its reconstruction and its QP probe
  *   batch_rate.hip    the plain rect's per-frame QP table and the pick on the device
  *   batch_hint.hip    UI hints, the rect under hints, the splice
@@ -11,6 +12,11 @@
  *   batch_mask.hip    the rect's per-MB source mask: difference map, keep decision, fill
  *   batch_detect.hip  each frame's scroll offset detected from the surfaces: signatures, scores, the choice
  *   batch_dropin.hip  the synchronous drop-in helpers of engine.h
+ * A side pass (the QP probe, the pick, the locate, the mask, the detect) is
+ * an asynchronous call beside the compose with device buffers of its own: it
+ * keeps its last run in a PassRun and, where it needs the compose's state
+ * pass, runs it dry into a DryPlan (and k_dyn_rows into a PredRows) through
+ * batch_pass.hip's helpers.  A new pass does the same.
  * Nothing here enters the library's dynamic symbol table.
  */
 #ifndef SCROLL_BATCH_H
@@ -43,7 +49,27 @@
 /* ScrollBatch                                                              */
 /* ======================================================================== */
 /* (the public headers' opaque type: global, and outside the hidden region
- * below, which would take its implicit members' symbols out of the library) */
+ * below, which would take its implicit members' symbols out of the library;
+ * so are the three records it holds by value) */
+/* a side pass's last run (batch_pass.hip) */
+struct PassRun {
+    int nframes = -1, nstreams = 0;    /* the last run; nframes -1: none */
+    int timed = 0;                     /* the last run recorded its timing events */
+    int nev = 0;                       /* the pass's timing events, ev[0 .. nev - 1] (pass_begin); 0: never timed */
+    hipEvent_t fin = nullptr;          /* recorded after the last run's launches */
+    hipEvent_t ev[5] = {};             /* timing: created on first use; those past nev stay null */
+};
+/* the compose's state pass into buffers of a side pass's own, nothing committed */
+struct DryPlan {
+    NalDesc *nal = nullptr;
+    DynFrame *dfr = nullptr;
+    PlanPending *pend = nullptr;
+};
+/* k_dyn_rows' prediction rows after a dry plan, as the compose keeps them in dx */
+struct PredRows {
+    uint32_t *rows = nullptr, *ctr = nullptr;
+    uint4 *heads = nullptr;
+};
 constexpr int NEV = 7;
 struct ScrollBatch {
     int device = 0;
@@ -99,19 +125,15 @@ struct ScrollBatch {
      * and its prediction rows in buffers of its own, so that nothing of the
      * batch's state is touched; allocated by the first probe */
     struct Probe {
-        NalDesc *nal = nullptr;
-        DynFrame *dfr = nullptr;
-        PlanPending *pend = nullptr;
-        uint32_t *rows = nullptr, *ctr = nullptr, *done = nullptr;
-        uint4 *heads = nullptr;
+        DryPlan plan;
+        PredRows pr;
+        uint32_t *done = nullptr;
         ScrollDynProbe *res = nullptr;  /* [max_streams * max_frames][SCROLL_DYN_PROBE_MAX_QPS] */
         uint8_t *cls = nullptr;         /* [max_streams * max_frames]: k_hprobe_class (scroll_batch_dyn_probe_hinted) */
         int hinted = 0;                 /* the last probe was the hinted one */
-        int nframes = -1, nstreams = 0, nq = 0;   /* the last probe; nframes -1: none */
-        uint8_t qps[SCROLL_DYN_PROBE_MAX_QPS] = {};   /* its candidates (scroll_batch_dyn_pick) */
-        hipEvent_t fin = nullptr;       /* recorded after the last probe's launches */
-        hipEvent_t ev[2] = {};          /* timing: around them (created on first use) */
-        int timed = 0;
+        int nq = 0;
+        uint8_t qps[SCROLL_DYN_PROBE_MAX_QPS] = {};   /* the last probe's candidates (scroll_batch_dyn_pick) */
+        PassRun run;                    /* ev[0..1]: around the probe's launches */
     } pb;
     /* the plain rect's per-frame QP table (dx.qpf, batch_rate.hip) and the
      * pick that fills it from the probe on the device (pick_kernels.hip);
@@ -122,51 +144,41 @@ struct ScrollBatch {
         long long *level = nullptr;     /* [max_streams]: the buckets' levels */
         uint32_t *fb = nullptr;         /* [max_streams]: frame_bits per stream of the last pick that gave them */
         PickOut *out = nullptr;         /* [max_streams * max_frames]: the last pick's choices */
-        hipEvent_t fin = nullptr;       /* recorded after the last pick's launch */
-        int nframes = -1, nstreams = 0; /* the last pick; nframes -1: none */
+        PassRun run;                    /* the last pick (no timing events) */
     } rt;
     /* pixels from renderer surfaces (batch_surface.hip, csc_kernels.hip):
      * nothing here exists before the first conversion */
     struct Surf {
         int32_t *pos = nullptr;         /* [nstreams * nframes][2]: the last call's per-frame rect origins (custom positions only) */
         std::vector<int32_t> h_pos;     /* what was uploaded there */
-        hipEvent_t fin = nullptr;       /* recorded after the last kernel that reads pos */
-        hipEvent_t ev[2] = {};          /* timing: around the last conversion (created on first use) */
-        int timed = 0;
+        /* recorded after the last kernel that reads pos: it guards pos and goes
+         * with the rect (surface_release).  Not the end of a run: run.fin below
+         * stays null, and nothing may wait on it or record it */
+        hipEvent_t fin = nullptr;
+        PassRun run;                    /* ev[0..1] and timed only: around the last conversion; kept with the batch */
     } sf;
     /* the rect located from the surfaces (scroll_batch_dyn_locate,
      * batch_damage.hip, damage_kernels.hip): a dry plan, the prediction rows
      * of whole pictures, the map and the records; nothing here exists before
      * the first locate, everything goes with the rect */
     struct Locate {
-        NalDesc *nal = nullptr;
-        DynFrame *dfr = nullptr;
-        PlanPending *pend = nullptr;
+        DryPlan plan;
         uint32_t *rows = nullptr;       /* [max_streams * max_frames][ph] */
         uint32_t *map = nullptr;        /* [max_streams * max_frames][mbh][mbw] */
         ScrollDynDamage *res = nullptr; /* [max_streams * max_frames] */
-        int nframes = -1, nstreams = 0; /* the last locate; nframes -1: none */
-        hipEvent_t fin = nullptr;       /* recorded after the last locate's launches */
-        hipEvent_t ev[4] = {};          /* timing: the call's start, around k_dyn_damage, its end (created on first use) */
-        int timed = 0;
+        PassRun run;                    /* ev[0..3]: the call's start, around k_dyn_damage, its end */
     } lc;
     /* the rect's per-MB source mask (scroll_batch_dyn_mask, batch_mask.hip,
      * mask_kernels.hip): a dry plan and its prediction rows as the probe keeps
      * them, the map, the rows' chroma partials and the records; nothing here
      * exists before the first mask, everything goes with the rect */
     struct Mask {
-        NalDesc *nal = nullptr;
-        DynFrame *dfr = nullptr;
-        PlanPending *pend = nullptr;
-        uint32_t *rows = nullptr, *ctr = nullptr;
-        uint4 *heads = nullptr;
+        DryPlan plan;
+        PredRows pr;
         uint32_t *map = nullptr;        /* [max_streams * max_frames][h][w][2] */
         unsigned long long *part = nullptr;   /* [max_streams * max_frames][h][2]: Cb, Cr dropped per rect row */
         ScrollDynMask *res = nullptr;   /* [max_streams * max_frames] */
-        int nframes = -1, nstreams = 0; /* the last mask; nframes -1: none */
-        hipEvent_t fin = nullptr;       /* recorded after the last mask's launches */
-        hipEvent_t ev[4] = {};          /* timing: the call's start, around k_dyn_mask_diff, its end (created on first use) */
-        int timed = 0;
+        PassRun run;                    /* ev[0..3]: the call's start, around k_dyn_mask_diff, its end */
     } mk;
     /* each frame's scroll offset detected from the surfaces
      * (scroll_batch_detect_offsets, batch_detect.hip, detect_kernels.hip):
@@ -177,10 +189,7 @@ struct ScrollBatch {
         uint16_t *sig_r = nullptr;      /* [max_streams][nseg][2 ph] */
         uint32_t *scores = nullptr;     /* [max_streams * max_frames][ph + 1] */
         ScrollOffsetFound *res = nullptr;   /* [max_streams * max_frames] */
-        int nframes = -1, nstreams = 0; /* the last detect; nframes -1: none */
-        hipEvent_t fin = nullptr;       /* recorded after the last detect's launches */
-        hipEvent_t ev[5] = {};          /* timing: the call's start, around k_det_surf, after k_det_score, its end (created on first use) */
-        int timed = 0;
+        PassRun run;                    /* ev[0..4]: the call's start, around k_det_surf, after k_det_score, its end */
     } dt;
     /* UI hints: staged like the dynamic rect (shares
      * d_dfr, d_stage and geo.slot_bytes; the two are exclusive) */
@@ -311,6 +320,38 @@ int batch_host_sync(ScrollBatch *b);
 int launch(ScrollBatch *b, int nframes, int plan_mode, int nal_max, hipStream_t hs, int plan_flags = 0);
 int stream_fail_code(ScrollBatch *b, int s);
 int load_nals(ScrollBatch *b);
+
+/* ---- batch_pass.hip ---- */
+/* waits for the last run, destroys the record's events and resets it */
+void pass_release(PassRun *r);
+/* a run begins on hs: not timed yet; with the batch's timing on, the pass's n
+ * events (those not there yet are created) and ev[0] recorded */
+int pass_begin(ScrollBatch *b, PassRun *r, int n, hipStream_t hs);
+/* ev[i] recorded, when the batch's timing is on */
+int pass_mark(ScrollBatch *b, PassRun *r, int i, hipStream_t hs);
+/* the timing's end: the pass's last event recorded, the run timed */
+int pass_stop(ScrollBatch *b, PassRun *r, hipStream_t hs);
+/* the run's end: pass_stop, fin recorded, the run of nframes x nstreams the last one */
+int pass_end(ScrollBatch *b, PassRun *r, hipStream_t hs, int nframes, int nstreams);
+/* a result call of `who` without a run to read (none yet, or released with
+ * the pass's buffers): SCROLL_ERR_CONFIG, "no <noun> to read (<entry>; ...)" */
+int pass_have(const PassRun *r, const char *who, const char *noun, const char *entry);
+/* the frame of the last run that a result call names: pass_have, stream and
+ * frame inside it (SCROLL_ERR_ARG); the run has finished on return */
+int pass_frame_arg(ScrollBatch *b, PassRun *r, int s, int f, const char *who, const char *noun, const char *entry);
+/* ms from ev[from] to ev[to] of the last run, once its last event has
+ * passed; -1 when it was not timed or the time cannot be read */
+float pass_span_ms(ScrollBatch *b, const PassRun *r, int from, int to);
+hipError_t dry_plan_alloc(const ScrollBatch *b, DryPlan *d);
+void dry_plan_free(DryPlan *d);
+/* k_plan's state pass for nframes of the batch's streams into d; ctr: the
+ * counters it zeroes, dpos: the moving rect's position table, or none */
+int dry_plan_launch(ScrollBatch *b, hipStream_t hs, int nframes, const DryPlan &d, int flags_extra = 0,
+                    uint32_t *ctr = nullptr, const uint32_t *dpos = nullptr);
+hipError_t pred_rows_alloc(const ScrollBatch *b, PredRows *p);
+void pred_rows_free(PredRows *p);
+/* k_dyn_rows after dry_plan_launch into p, G->gen_cap a slot for every frame; no per-frame QP table */
+int pred_rows_launch(ScrollBatch *b, hipStream_t hs, int nframes, const DryPlan &d, const PredRows &p, DynGeom *G);
 
 /* ---- batch_dyn.hip ---- */
 void probe_release(ScrollBatch *b);

@@ -10,7 +10,6 @@
 #include <stdint.h>
 
 #include "batch.h"
-#include "scroll_engine.h"
 #include "csc_device.h"
 #include "damage_engine.h"
 #include "dyn_pos.h"            /* dyn_pos_unpack: the position table's word */
@@ -23,15 +22,8 @@ namespace batch {
 void locate_release(ScrollBatch *b)
 {
     ScrollBatch::Locate &l = b->lc;
-    if (l.fin) {
-        (void)hipEventSynchronize(l.fin);
-        (void)hipEventDestroy(l.fin);
-    }
-    for (hipEvent_t e : l.ev)
-        if (e) (void)hipEventDestroy(e);
-    (void)hipFree(l.nal);
-    (void)hipFree(l.dfr);
-    (void)hipFree(l.pend);
+    pass_release(&l.run);
+    dry_plan_free(&l.plan);
     (void)hipFree(l.rows);
     (void)hipFree(l.map);
     (void)hipFree(l.res);
@@ -86,39 +78,19 @@ static int locate_alloc(ScrollBatch *b, const char *who)
 {
     ScrollBatch::Locate &l = b->lc;
     if (l.res) return SCROLL_OK;
-    const size_t S = (size_t)b->max_streams, NF = S * (size_t)b->max_frames;
+    const size_t NF = (size_t)b->max_streams * (size_t)b->max_frames;
     const size_t nmb = (size_t)(b->dyn_pw / 16) * (b->dyn_ph / 16);
-    hipError_t e = hipMalloc(&l.nal, S * (size_t)b->ld_nal * sizeof(NalDesc));
-    if (e == hipSuccess) e = hipMalloc(&l.dfr, NF * sizeof(DynFrame));
-    if (e == hipSuccess) e = hipMalloc(&l.pend, S * sizeof(PlanPending));
+    hipError_t e = dry_plan_alloc(b, &l.plan);
     if (e == hipSuccess) e = hipMalloc(&l.rows, NF * (size_t)b->dyn_ph * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&l.map, NF * nmb * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&l.res, NF * sizeof(ScrollDynDamage));
     if (e == hipSuccess) e = hipMemset(l.map, 0, NF * nmb * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(l.res, 0, NF * sizeof(ScrollDynDamage));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&l.fin, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&l.run.fin, hipEventDisableTiming);
     if (e != hipSuccess) {
         locate_release(b);
         return hip_fail(who, e, true);
     }
-    return SCROLL_OK;
-}
-
-/* the frame of the last locate that a result call names; the locate has finished on return */
-static int locate_frame_arg(ScrollBatch *b, int s, int f, const char *who)
-{
-    if (!b) return SCROLL_ERR_ARG;
-    ScrollBatch::Locate &l = b->lc;
-    if (!l.res || l.nframes < 0) {
-        set_err("%s: no locate to read (scroll_batch_dyn_locate; scroll_batch_set_dyn_rect drops it)", who);
-        return SCROLL_ERR_CONFIG;
-    }
-    if (s < 0 || s >= l.nstreams || f < 0 || f >= l.nframes) {
-        set_err("%s: stream %d / frame %d outside the last locate", who, s, f);
-        return SCROLL_ERR_ARG;
-    }
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(hipEventSynchronize(l.fin));
     return SCROLL_OK;
 }
 
@@ -194,11 +166,7 @@ int scroll_batch_dyn_locate(ScrollBatch *b, int nframes, const ScrollSurfaces *s
     if (rr) return rr;
     ScrollBatch::Locate &l = b->lc;
     hipStream_t hs = hip_stream ? (hipStream_t)hip_stream : b->own;
-    const bool timed = b->timing != 0;
-    l.timed = 0;
-    if (timed && !l.ev[0])
-        for (hipEvent_t &e : l.ev) HIPCHK(hipEventCreate(&e));
-    if (timed) HIPCHK(hipEventRecord(l.ev[0], hs));
+    if ((rr = pass_begin(b, &l.run, 4, hs))) return rr;
 
     uint32_t *dpos = nullptr;
     if (rule->apply) {
@@ -220,38 +188,30 @@ int scroll_batch_dyn_locate(ScrollBatch *b, int nframes, const ScrollSurfaces *s
     }
 
     /* the compose's state pass, dry, as the QP probe runs it (probe_run):
-     * into the locate's own NalDesc / DynFrame / PlanPending, nothing
-     * committed.  No position table: every frame with a scroll NAL has
-     * DynFrame.nal >= 0, wherever its rect was before */
-    const int plan = b->mode == SCROLL_MODE_EXPERIMENT ? SCROLL_PLAN_EXPERIMENT : SCROLL_PLAN_COMPOSER;
-    scroll_launch_plan(hs, S, b->d_st, b->d_off, b->max_frames, l.nal, b->ld_nal, nframes, plan,
-                       (b->debug & (PLAN_REWIND - 1)) | PLAN_STATE | PLAN_DYN, l.pend, l.dfr, ld_fr);
-    HIPCHK(hipGetLastError());
-    if (dmg_launch_rows(hs, nframes, S, b->d_st, l.nal, b->ld_nal, l.pend, l.dfr, ld_fr, b->dyn_ph, l.rows)) {
+     * into the locate's own DryPlan, nothing committed.  No position table:
+     * every frame with a scroll NAL has DynFrame.nal >= 0, wherever its rect
+     * was before */
+    if ((rr = dry_plan_launch(b, hs, nframes, l.plan))) return rr;
+    if (dmg_launch_rows(hs, nframes, S, b->d_st, l.plan.nal, b->ld_nal, l.plan.pend, l.plan.dfr, ld_fr, b->dyn_ph,
+                        l.rows)) {
         set_err("k_dmg_rows launch: %s", hipGetErrorString(hipGetLastError()));
         return SCROLL_ERR_HIP;
     }
     job.rows = l.rows;
-    job.dfr = l.dfr;
+    job.dfr = l.plan.dfr;
     job.map = l.map;
-    if (timed) HIPCHK(hipEventRecord(l.ev[1], hs));
+    if ((rr = pass_mark(b, &l.run, 1, hs))) return rr;
     if (dmg_launch_damage(hs, &job)) {
         set_err("k_dyn_damage launch: %s", hipGetErrorString(hipGetLastError()));
         return SCROLL_ERR_HIP;
     }
-    if (timed) HIPCHK(hipEventRecord(l.ev[2], hs));
-    if (dmg_launch_place(hs, nframes, S, l.dfr, ld_fr, l.map, mbw, mbh, (uint32_t)b->geo.w, (uint32_t)b->geo.h, rule,
-                         l.res, dpos)) {
+    if ((rr = pass_mark(b, &l.run, 2, hs))) return rr;
+    if (dmg_launch_place(hs, nframes, S, l.plan.dfr, ld_fr, l.map, mbw, mbh, (uint32_t)b->geo.w, (uint32_t)b->geo.h,
+                         rule, l.res, dpos)) {
         set_err("k_dyn_place launch: %s", hipGetErrorString(hipGetLastError()));
         return SCROLL_ERR_HIP;
     }
-    if (timed) {
-        HIPCHK(hipEventRecord(l.ev[3], hs));
-        l.timed = 1;
-    }
-    HIPCHK(hipEventRecord(l.fin, hs));
-    l.nframes = nframes;
-    l.nstreams = S;
+    if ((rr = pass_end(b, &l.run, hs, nframes, S))) return rr;
     if (dpos) {
         /* from here the device's table is the truth (dyn_pos_table hands it
          * out as it is; dyn_pos_refresh brings the host's copy up to date) */
@@ -266,8 +226,8 @@ int scroll_batch_dyn_locate(ScrollBatch *b, int nframes, const ScrollSurfaces *s
 
 int scroll_batch_dyn_locate_result(ScrollBatch *b, int s, int f, ScrollDynDamage *out)
 {
-    if (!out) return SCROLL_ERR_ARG;
-    int rc = locate_frame_arg(b, s, f, "scroll_batch_dyn_locate_result");
+    if (!b || !out) return SCROLL_ERR_ARG;
+    int rc = pass_frame_arg(b, &b->lc.run, s, f, "scroll_batch_dyn_locate_result", "locate", "scroll_batch_dyn_locate");
     if (rc) return rc;
     HIPCHK(hipMemcpy(out, b->lc.res + (size_t)s * b->max_frames + f, sizeof(*out), hipMemcpyDeviceToHost));
     return SCROLL_OK;
@@ -282,8 +242,8 @@ const ScrollDynDamage *scroll_batch_dyn_locate_device(ScrollBatch *b, size_t *st
 
 int scroll_batch_dyn_damage_map(ScrollBatch *b, int s, int f, uint32_t *dst)
 {
-    if (!dst) return SCROLL_ERR_ARG;
-    int rc = locate_frame_arg(b, s, f, "scroll_batch_dyn_damage_map");
+    if (!b || !dst) return SCROLL_ERR_ARG;
+    int rc = pass_frame_arg(b, &b->lc.run, s, f, "scroll_batch_dyn_damage_map", "locate", "scroll_batch_dyn_locate");
     if (rc) return rc;
     const size_t nmb = (size_t)(b->dyn_pw / 16) * (b->dyn_ph / 16);
     HIPCHK(hipMemcpy(dst, b->lc.map + ((size_t)s * b->max_frames + f) * nmb, nmb * sizeof(uint32_t),
@@ -300,23 +260,8 @@ const uint32_t *scroll_batch_dyn_damage_map_device(ScrollBatch *b, size_t *strea
     return b->lc.map;
 }
 
-static float locate_span_ms(ScrollBatch *b, int from, int to)
-{
-    if (!b || !b->lc.res || !b->lc.timed) return -1.0f;
-    if (hipSetDevice(b->device) != hipSuccess || hipEventSynchronize(b->lc.ev[3]) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0f;
-    }
-    float ms = -1.0f;
-    if (hipEventElapsedTime(&ms, b->lc.ev[from], b->lc.ev[to]) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0f;
-    }
-    return ms;
-}
+float scroll_batch_dyn_locate_ms(ScrollBatch *b) { return b ? pass_span_ms(b, &b->lc.run, 0, 3) : -1.0f; }
 
-float scroll_batch_dyn_locate_ms(ScrollBatch *b) { return locate_span_ms(b, 0, 3); }
-
-float scroll_batch_dyn_locate_kernel_ms(ScrollBatch *b) { return locate_span_ms(b, 1, 2); }
+float scroll_batch_dyn_locate_kernel_ms(ScrollBatch *b) { return b ? pass_span_ms(b, &b->lc.run, 1, 2) : -1.0f; }
 
 }  // extern "C"

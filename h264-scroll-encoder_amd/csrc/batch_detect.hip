@@ -22,12 +22,7 @@ namespace batch {
 void detect_release(ScrollBatch *b)
 {
     ScrollBatch::Detect &d = b->dt;
-    if (d.fin) {
-        (void)hipEventSynchronize(d.fin);
-        (void)hipEventDestroy(d.fin);
-    }
-    for (hipEvent_t e : d.ev)
-        if (e) (void)hipEventDestroy(e);
+    pass_release(&d.run);
     (void)hipFree(d.sig_s);
     (void)hipFree(d.sig_r);
     (void)hipFree(d.scores);
@@ -51,29 +46,11 @@ static int detect_alloc(ScrollBatch *b, const char *who)
     if (e == hipSuccess) e = hipMalloc(&d.res, NF * sizeof(ScrollOffsetFound));
     if (e == hipSuccess) e = hipMemset(d.scores, 0xFF, NF * (ph + 1u) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(d.res, 0, NF * sizeof(ScrollOffsetFound));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&d.fin, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&d.run.fin, hipEventDisableTiming);
     if (e != hipSuccess) {
         detect_release(b);
         return hip_fail(who, e, true);
     }
-    return SCROLL_OK;
-}
-
-/* the frame of the last detect that a result call names; the detect has finished on return */
-static int detect_frame_arg(ScrollBatch *b, int s, int f, const char *who)
-{
-    if (!b) return SCROLL_ERR_ARG;
-    ScrollBatch::Detect &d = b->dt;
-    if (!d.res || d.nframes < 0) {
-        set_err("%s: no detect to read (scroll_batch_detect_offsets; scroll_batch_set_dyn_rect drops it)", who);
-        return SCROLL_ERR_CONFIG;
-    }
-    if (s < 0 || s >= d.nstreams || f < 0 || f >= d.nframes) {
-        set_err("%s: stream %d / frame %d outside the last detect", who, s, f);
-        return SCROLL_ERR_ARG;
-    }
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(hipEventSynchronize(d.fin));
     return SCROLL_OK;
 }
 
@@ -145,46 +122,36 @@ int scroll_batch_detect_offsets(ScrollBatch *b, int nframes, const ScrollSurface
     job.k = scroll::csc::coef(surf->format, surf->matrix, surf->full_range);
 
     hipStream_t hs = hip_stream ? (hipStream_t)hip_stream : b->own;
-    const bool timed = b->timing != 0;
-    d.timed = 0;
-    if (timed && !d.ev[0])
-        for (hipEvent_t &e : d.ev) HIPCHK(hipEventCreate(&e));
-    if (timed) HIPCHK(hipEventRecord(d.ev[0], hs));
+    int tr = pass_begin(b, &d.run, 5, hs);
+    if (tr) return tr;
     /* the references' signatures every call: a cache would have to be
      * invalidated by every call that writes a reference picture */
     if (det_launch_refs(hs, &job)) {
         set_err("k_det_refs launch: %s", hipGetErrorString(hipGetLastError()));
         return SCROLL_ERR_HIP;
     }
-    if (timed) HIPCHK(hipEventRecord(d.ev[1], hs));
+    if ((tr = pass_mark(b, &d.run, 1, hs))) return tr;
     if (det_launch_surf(hs, &job)) {
         set_err("k_det_surf launch: %s", hipGetErrorString(hipGetLastError()));
         return SCROLL_ERR_HIP;
     }
-    if (timed) HIPCHK(hipEventRecord(d.ev[2], hs));
+    if ((tr = pass_mark(b, &d.run, 2, hs))) return tr;
     if (det_launch_score(hs, &job)) {
         set_err("k_det_score launch: %s", hipGetErrorString(hipGetLastError()));
         return SCROLL_ERR_HIP;
     }
-    if (timed) HIPCHK(hipEventRecord(d.ev[3], hs));
+    if ((tr = pass_mark(b, &d.run, 3, hs))) return tr;
     if (det_launch_pick(hs, &job)) {
         set_err("k_det_pick launch: %s", hipGetErrorString(hipGetLastError()));
         return SCROLL_ERR_HIP;
     }
-    if (timed) {
-        HIPCHK(hipEventRecord(d.ev[4], hs));
-        d.timed = 1;
-    }
-    HIPCHK(hipEventRecord(d.fin, hs));
-    d.nframes = nframes;
-    d.nstreams = S;
-    return SCROLL_OK;
+    return pass_end(b, &d.run, hs, nframes, S);
 }
 
 int scroll_batch_detect_result(ScrollBatch *b, int s, int f, ScrollOffsetFound *out)
 {
-    if (!out) return SCROLL_ERR_ARG;
-    int rc = detect_frame_arg(b, s, f, "scroll_batch_detect_result");
+    if (!b || !out) return SCROLL_ERR_ARG;
+    int rc = pass_frame_arg(b, &b->dt.run, s, f, "scroll_batch_detect_result", "detect", "scroll_batch_detect_offsets");
     if (rc) return rc;
     HIPCHK(hipMemcpy(out, b->dt.res + (size_t)s * b->max_frames + f, sizeof(*out), hipMemcpyDeviceToHost));
     return SCROLL_OK;
@@ -199,8 +166,8 @@ const ScrollOffsetFound *scroll_batch_detect_device(ScrollBatch *b, size_t *stre
 
 int scroll_batch_detect_scores(ScrollBatch *b, int s, int f, uint32_t *dst)
 {
-    if (!dst) return SCROLL_ERR_ARG;
-    int rc = detect_frame_arg(b, s, f, "scroll_batch_detect_scores");
+    if (!b || !dst) return SCROLL_ERR_ARG;
+    int rc = pass_frame_arg(b, &b->dt.run, s, f, "scroll_batch_detect_scores", "detect", "scroll_batch_detect_offsets");
     if (rc) return rc;
     const size_t n = (size_t)b->dyn_ph + 1u;
     HIPCHK(hipMemcpy(dst, b->dt.scores + ((size_t)s * b->max_frames + f) * n, n * sizeof(uint32_t),
@@ -217,26 +184,11 @@ const uint32_t *scroll_batch_detect_scores_device(ScrollBatch *b, size_t *stream
     return b->dt.scores;
 }
 
-static float detect_span_ms(ScrollBatch *b, int from, int to)
-{
-    if (!b || !b->dt.res || !b->dt.timed) return -1.0f;
-    if (hipSetDevice(b->device) != hipSuccess || hipEventSynchronize(b->dt.ev[4]) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0f;
-    }
-    float ms = -1.0f;
-    if (hipEventElapsedTime(&ms, b->dt.ev[from], b->dt.ev[to]) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0f;
-    }
-    return ms;
-}
+float scroll_batch_detect_ms(ScrollBatch *b) { return b ? pass_span_ms(b, &b->dt.run, 0, 4) : -1.0f; }
 
-float scroll_batch_detect_ms(ScrollBatch *b) { return detect_span_ms(b, 0, 4); }
-
-float scroll_batch_detect_kernel_ms(ScrollBatch *b) { return detect_span_ms(b, 1, 2); }
+float scroll_batch_detect_kernel_ms(ScrollBatch *b) { return b ? pass_span_ms(b, &b->dt.run, 1, 2) : -1.0f; }
 
 /* the score stage alone (k_det_score and k_det_pick): what tools/detect_bench.py reports beside the kernel */
-float scroll_batch_detect_score_ms(ScrollBatch *b) { return detect_span_ms(b, 2, 4); }
+float scroll_batch_detect_score_ms(ScrollBatch *b) { return b ? pass_span_ms(b, &b->dt.run, 2, 4) : -1.0f; }
 
 }  // extern "C"

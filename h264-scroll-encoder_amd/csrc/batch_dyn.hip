@@ -28,19 +28,10 @@ namespace batch {
 void probe_release(ScrollBatch *b)
 {
     ScrollBatch::Probe &p = b->pb;
-    if (p.fin) {
-        (void)hipEventSynchronize(p.fin);
-        (void)hipEventDestroy(p.fin);
-    }
-    for (hipEvent_t e : p.ev)
-        if (e) (void)hipEventDestroy(e);
-    (void)hipFree(p.nal);
-    (void)hipFree(p.dfr);
-    (void)hipFree(p.pend);
-    (void)hipFree(p.rows);
-    (void)hipFree(p.ctr);
+    pass_release(&p.run);
+    dry_plan_free(&p.plan);
+    pred_rows_free(&p.pr);
     (void)hipFree(p.done);
-    (void)hipFree(p.heads);
     (void)hipFree(p.res);
     (void)hipFree(p.cls);
     p = ScrollBatch::Probe{};
@@ -203,17 +194,12 @@ static int probe_alloc(ScrollBatch *b)
 {
     ScrollBatch::Probe &p = b->pb;
     if (p.res) return SCROLL_OK;
-    const size_t S = (size_t)b->max_streams, NF = S * (size_t)b->max_frames;
-    hipError_t e = hipMalloc(&p.nal, S * (size_t)b->ld_nal * sizeof(NalDesc));
-    if (e == hipSuccess) e = hipMalloc(&p.dfr, NF * sizeof(DynFrame));
-    if (e == hipSuccess) e = hipMalloc(&p.pend, S * sizeof(PlanPending));
-    if (e == hipSuccess) e = hipMalloc(&p.rows, NF * 32 * (size_t)b->geo.h * sizeof(uint32_t));
-    /* the general-frame list holds every frame: it can never run out */
-    if (e == hipSuccess) e = hipMalloc(&p.ctr, (DYN_CTR_LIST + NF) * sizeof(uint32_t));
+    const size_t NF = (size_t)b->max_streams * (size_t)b->max_frames;
+    hipError_t e = dry_plan_alloc(b, &p.plan);
+    if (e == hipSuccess) e = pred_rows_alloc(b, &p.pr);
     if (e == hipSuccess) e = hipMalloc(&p.done, NF * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&p.heads, NF * DYN_HEAD_VECS * sizeof(uint4));
     if (e == hipSuccess) e = hipMalloc(&p.res, NF * SCROLL_DYN_PROBE_MAX_QPS * sizeof(ScrollDynProbe));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p.fin, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&p.run.fin, hipEventDisableTiming);
     if (e != hipSuccess) {
         probe_release(b);
         return hip_fail("scroll_batch_dyn_probe", e, true);
@@ -249,44 +235,38 @@ static int probe_args(ScrollBatch *b, const char *who, int nframes, const uint8_
 }
 
 /* a probe of nframes frames at nq candidates, once its buffers are there:
- * the compose's state pass into the probe's own NalDesc / DynFrame /
- * PlanPending (k_plan with PLAN_STATE reads the streams and commits
- * nothing; ctr: the counters it zeroes, or none), then the probe's own
- * launches: own(hs, S, G, ev1), ev1 to record after them when timed */
+ * the compose's state pass into the probe's own DryPlan (k_plan with
+ * PLAN_STATE reads the streams and commits nothing; ctr: the counters it
+ * zeroes, or none), then the probe's own launches: own(hs, S, G, ev1), ev1 to
+ * record after them when timed.  The run is stored before the launches, and
+ * fin recorded, for a probe of no frames too: it is a valid last probe, which
+ * a pick of 0 frames may follow */
 template <class Own>
 static int probe_run(ScrollBatch *b, int nframes, const ProbeQps &Q, void *hip_stream, int hinted, uint32_t *ctr,
                      Own own)
 {
     ScrollBatch::Probe &p = b->pb;
     hipStream_t hs = hip_stream ? (hipStream_t)hip_stream : b->own;
-    const int S = b->nstreams, ld_fr = b->max_frames, nq = Q.n;
-    p.nframes = nframes;
-    p.nstreams = S;
+    const int S = b->nstreams, nq = Q.n;
+    p.run.nframes = nframes;
+    p.run.nstreams = S;
     p.nq = nq;
     for (int k = 0; k < nq; ++k) p.qps[k] = Q.qp[k];
-    p.timed = 0;
+    p.run.timed = 0;
     p.hinted = hinted;
     if (S > 0 && nframes > 0) {
         const bool timed = b->timing != 0;
-        if (timed && !p.ev[0]) {
-            HIPCHK(hipEventCreate(&p.ev[0]));
-            HIPCHK(hipEventCreate(&p.ev[1]));
-        }
-        if (timed) HIPCHK(hipEventRecord(p.ev[0], hs));
+        int rc = pass_begin(b, &p.run, 2, hs);
+        if (rc) return rc;
         DynGeom G = b->geo;
         G.debug = b->debug;
         /* moving rects (never under hints): the frames' own origins, and no dynamic NAL where there is no rect */
-        int prc = dyn_pos_table(b, hs, &G.dpos);
-        if (prc) return prc;
-        const int plan = b->mode == SCROLL_MODE_EXPERIMENT ? SCROLL_PLAN_EXPERIMENT : SCROLL_PLAN_COMPOSER;
-        scroll_launch_plan(hs, S, b->d_st, b->d_off, b->max_frames, p.nal, b->ld_nal, nframes, plan,
-                           b->debug | PLAN_STATE | PLAN_DYN, p.pend, p.dfr, ld_fr, nullptr, 0u, 0u, ctr, G.dpos);
-        HIPCHK(hipGetLastError());
-        const int rc = own(hs, S, G, timed ? p.ev[1] : nullptr);
-        if (rc) return rc;
-        p.timed = timed ? 1 : 0;
+        if ((rc = dyn_pos_table(b, hs, &G.dpos))) return rc;
+        if ((rc = dry_plan_launch(b, hs, nframes, p.plan, 0, ctr, G.dpos))) return rc;
+        if ((rc = own(hs, S, G, timed ? p.run.ev[1] : nullptr))) return rc;
+        p.run.timed = timed ? 1 : 0;
     }
-    HIPCHK(hipEventRecord(p.fin, hs));
+    HIPCHK(hipEventRecord(p.run.fin, hs));
     return SCROLL_OK;
 }
 
@@ -355,7 +335,7 @@ int dyn_sizes_enable(ScrollBatch *b, const char *who)
     int rc = batch_host_sync(b);
     if (rc) return rc;
     HIPCHK(hipSetDevice(b->device));
-    if (b->pb.fin) HIPCHK(hipEventSynchronize(b->pb.fin));     /* a probe on another stream */
+    if (b->pb.run.fin) HIPCHK(hipEventSynchronize(b->pb.run.fin));     /* a probe on another stream */
     if (b->dpos_ev) HIPCHK(hipEventSynchronize(b->dpos_ev));   /* an upload or a locate */
     DynGeom g = b->geo;
     dyn_rowstage_geom(&g, b->dyn_pw / 16, b->dyn_ph / 16, 2);
@@ -555,7 +535,7 @@ int scroll_batch_set_dyn_rect_at(ScrollBatch *b, int s, int f, int x0, int y0)
     int rc = batch_host_sync(b);
     if (rc) return rc;
     /* with moving rects a probe on a stream of its own may still read the device table */
-    if (b->dyn_moving && b->pb.fin) HIPCHK(hipEventSynchronize(b->pb.fin));
+    if (b->dyn_moving && b->pb.run.fin) HIPCHK(hipEventSynchronize(b->pb.run.fin));
     /* positions a locate placed on the device stay, all but this one */
     if ((rc = dyn_pos_refresh(b))) return rc;
     const size_t i = (size_t)s * b->max_frames + f;
@@ -587,7 +567,7 @@ int scroll_batch_set_dyn_rect_moving(ScrollBatch *b, int on)
     int rc = batch_host_sync(b);
     if (rc) return rc;
     HIPCHK(hipSetDevice(b->device));
-    if (b->pb.fin) HIPCHK(hipEventSynchronize(b->pb.fin));     /* a probe on another stream */
+    if (b->pb.run.fin) HIPCHK(hipEventSynchronize(b->pb.run.fin));     /* a probe on another stream */
     if (b->dpos_ev) HIPCHK(hipEventSynchronize(b->dpos_ev));
     if ((rc = dyn_pos_refresh(b))) return rc;                   /* located positions outlive the table */
     if (!on && b->dsz_on) {                                     /* sizes need the flag: they go with it */
@@ -650,7 +630,7 @@ int scroll_batch_set_dyn_rect_size_at(ScrollBatch *b, int s, int f, int w, int h
     if (rc) return rc;
     if ((rc = batch_host_sync(b))) return rc;
     /* a probe on a stream of its own may still read the device table */
-    if (b->pb.fin) HIPCHK(hipEventSynchronize(b->pb.fin));
+    if (b->pb.run.fin) HIPCHK(hipEventSynchronize(b->pb.run.fin));
     /* what a locate placed on the device stays, all but this frame's size */
     if ((rc = dyn_pos_refresh(b))) return rc;
     const size_t i = (size_t)s * b->max_frames + f;
@@ -999,16 +979,12 @@ int scroll_batch_dyn_probe(ScrollBatch *b, int nframes, const uint8_t *qps, int 
     ScrollBatch::Probe &p = b->pb;
     const int ld_fr = b->max_frames;
     /* k_dyn_rows after the state pass, into the probe's own rows / heads / ctr */
-    return probe_run(b, nframes, Q, hip_stream, 0, p.ctr, [&](hipStream_t hs, int S, DynGeom &G, hipEvent_t ev1) {
-        G.gen_cap = (uint32_t)((size_t)b->max_streams * ld_fr);
+    return probe_run(b, nframes, Q, hip_stream, 0, p.pr.ctr, [&](hipStream_t hs, int S, DynGeom &G, hipEvent_t ev1) {
         /* (no per-frame QP table: the probe's QPs are its arguments) */
-        if (dyn_launch_rows(hs, nframes, S, b->d_st, p.nal, b->ld_nal, p.pend, p.dfr, ld_fr, &G, p.rows, p.ctr,
-                            p.heads, nullptr)) {
-            set_err("k_dyn_rows launch: %s", hipGetErrorString(hipGetLastError()));
-            return SCROLL_ERR_HIP;
-        }
-        if (probe_launch(hs, nframes, S, b->d_st, p.nal, b->ld_nal, p.pend, p.dfr, ld_fr, &G, p.rows, b->d_src,
-                         b->d_refs, &Q, p.res, p.done, p.ctr, nullptr, ev1)) {
+        const int rr = pred_rows_launch(b, hs, nframes, p.plan, p.pr, &G);
+        if (rr) return rr;
+        if (probe_launch(hs, nframes, S, b->d_st, p.plan.nal, b->ld_nal, p.plan.pend, p.plan.dfr, ld_fr, &G,
+                         p.pr.rows, b->d_src, b->d_refs, &Q, p.res, p.done, p.pr.ctr, nullptr, ev1)) {
             set_err("k_dyn_probe launch: %s", hipGetErrorString(hipGetLastError()));
             return SCROLL_ERR_HIP;
         }
@@ -1059,8 +1035,8 @@ int scroll_batch_dyn_probe_hinted(ScrollBatch *b, int nframes, const uint8_t *qp
     const int ld_fr = b->max_frames;
     /* no k_dyn_rows after the state pass (the motion is the hints'), and no counters for it to zero */
     return probe_run(b, nframes, Q, hip_stream, 1, nullptr, [&](hipStream_t hs, int S, DynGeom &G, hipEvent_t ev1) {
-        if (hprobe_launch(hs, nframes, S, b->d_st, p.nal, b->ld_nal, p.pend, p.dfr, ld_fr, b->d_hf, b->d_pool,
-                          b->d_spf, b->fallback, &G, b->d_src, b->d_refs, &Q, p.cls, p.res, p.done, ev1)) {
+        if (hprobe_launch(hs, nframes, S, b->d_st, p.plan.nal, b->ld_nal, p.plan.pend, p.plan.dfr, ld_fr, b->d_hf,
+                          b->d_pool, b->d_spf, b->fallback, &G, b->d_src, b->d_refs, &Q, p.cls, p.res, p.done, ev1)) {
             set_err("k_hdyn_probe launch: %s", hipGetErrorString(hipGetLastError()));
             return SCROLL_ERR_HIP;
         }
@@ -1072,20 +1048,18 @@ int scroll_batch_dyn_probe_result(ScrollBatch *b, int s, int f, int k, ScrollDyn
 {
     if (!b || !out) return SCROLL_ERR_ARG;
     ScrollBatch::Probe &p = b->pb;
-    if (!p.res || p.nframes < 0) {
-        set_err("scroll_batch_dyn_probe_result: no probe to read (scroll_batch_dyn_probe; "
-                "scroll_batch_set_dyn_rect drops it)");
-        return SCROLL_ERR_CONFIG;
-    }
-    if (s < 0 || s >= p.nstreams || f < 0 || f >= p.nframes || k < 0 || k >= p.nq) {
+    /* (the range message names the candidate too: pass_frame_arg's first half only) */
+    const int rc = pass_have(&p.run, "scroll_batch_dyn_probe_result", "probe", "scroll_batch_dyn_probe");
+    if (rc) return rc;
+    if (s < 0 || s >= p.run.nstreams || f < 0 || f >= p.run.nframes || k < 0 || k >= p.nq) {
         set_err("scroll_batch_dyn_probe_result: stream %d / frame %d / candidate %d outside the last probe", s, f, k);
         return SCROLL_ERR_ARG;
     }
     HIPCHK(hipSetDevice(b->device));
-    HIPCHK(hipEventSynchronize(p.fin));
+    HIPCHK(hipEventSynchronize(p.run.fin));
     const size_t fi = (size_t)s * b->max_frames + f;
     DynFrame d;
-    HIPCHK(hipMemcpy(&d, p.dfr + fi, sizeof(d), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&d, p.plan.dfr + fi, sizeof(d), hipMemcpyDeviceToHost));
     if (d.nal < 0) return 1;
     if (p.hinted) {
         uint8_t c = 0;
@@ -1116,19 +1090,6 @@ const ScrollDynProbe *scroll_batch_dyn_probe_device(ScrollBatch *b, size_t *stre
     return b->pb.res;
 }
 
-float scroll_batch_dyn_probe_ms(ScrollBatch *b)
-{
-    if (!b || !b->pb.res || !b->pb.timed) return -1.0f;
-    if (hipEventSynchronize(b->pb.ev[1]) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0f;
-    }
-    float ms = -1.0f;
-    if (hipEventElapsedTime(&ms, b->pb.ev[0], b->pb.ev[1]) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0f;
-    }
-    return ms;
-}
+float scroll_batch_dyn_probe_ms(ScrollBatch *b) { return b ? pass_span_ms(b, &b->pb.run, 0, 1) : -1.0f; }
 
 }  // extern "C"

@@ -10,8 +10,6 @@
 #include <stdint.h>
 
 #include "batch.h"
-#include "scroll_engine.h"
-#include "dyn_engine.h"
 #include "mask_device.h"
 #include "mask_engine.h"
 
@@ -23,18 +21,9 @@ namespace batch {
 void mask_release(ScrollBatch *b)
 {
     ScrollBatch::Mask &m = b->mk;
-    if (m.fin) {
-        (void)hipEventSynchronize(m.fin);
-        (void)hipEventDestroy(m.fin);
-    }
-    for (hipEvent_t e : m.ev)
-        if (e) (void)hipEventDestroy(e);
-    (void)hipFree(m.nal);
-    (void)hipFree(m.dfr);
-    (void)hipFree(m.pend);
-    (void)hipFree(m.rows);
-    (void)hipFree(m.ctr);
-    (void)hipFree(m.heads);
+    pass_release(&m.run);
+    dry_plan_free(&m.plan);
+    pred_rows_free(&m.pr);
     (void)hipFree(m.map);
     (void)hipFree(m.part);
     (void)hipFree(m.res);
@@ -50,42 +39,19 @@ static int mask_alloc(ScrollBatch *b, const char *who)
 {
     ScrollBatch::Mask &m = b->mk;
     if (m.res) return SCROLL_OK;
-    const size_t S = (size_t)b->max_streams, NF = S * (size_t)b->max_frames, h = (size_t)b->geo.h;
-    hipError_t e = hipMalloc(&m.nal, S * (size_t)b->ld_nal * sizeof(NalDesc));
-    if (e == hipSuccess) e = hipMalloc(&m.dfr, NF * sizeof(DynFrame));
-    if (e == hipSuccess) e = hipMalloc(&m.pend, S * sizeof(PlanPending));
-    if (e == hipSuccess) e = hipMalloc(&m.rows, NF * 32 * h * sizeof(uint32_t));
-    /* the general-frame list holds every frame: it can never run out */
-    if (e == hipSuccess) e = hipMalloc(&m.ctr, (DYN_CTR_LIST + NF) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&m.heads, NF * DYN_HEAD_VECS * sizeof(uint4));
+    const size_t NF = (size_t)b->max_streams * (size_t)b->max_frames, h = (size_t)b->geo.h;
+    hipError_t e = dry_plan_alloc(b, &m.plan);
+    if (e == hipSuccess) e = pred_rows_alloc(b, &m.pr);
     if (e == hipSuccess) e = hipMalloc(&m.map, NF * mask_frame_words(b) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&m.part, NF * h * 2 * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc(&m.res, NF * sizeof(ScrollDynMask));
     if (e == hipSuccess) e = hipMemset(m.map, 0, NF * mask_frame_words(b) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(m.res, 0, NF * sizeof(ScrollDynMask));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&m.fin, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&m.run.fin, hipEventDisableTiming);
     if (e != hipSuccess) {
         mask_release(b);
         return hip_fail(who, e, true);
     }
-    return SCROLL_OK;
-}
-
-/* the frame of the last mask that a result call names; the mask has finished on return */
-static int mask_frame_arg(ScrollBatch *b, int s, int f, const char *who)
-{
-    if (!b) return SCROLL_ERR_ARG;
-    ScrollBatch::Mask &m = b->mk;
-    if (!m.res || m.nframes < 0) {
-        set_err("%s: no mask to read (scroll_batch_dyn_mask; scroll_batch_set_dyn_rect drops it)", who);
-        return SCROLL_ERR_CONFIG;
-    }
-    if (s < 0 || s >= m.nstreams || f < 0 || f >= m.nframes) {
-        set_err("%s: stream %d / frame %d outside the last mask", who, s, f);
-        return SCROLL_ERR_ARG;
-    }
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(hipEventSynchronize(m.fin));
     return SCROLL_OK;
 }
 
@@ -131,35 +97,24 @@ int scroll_batch_dyn_mask(ScrollBatch *b, int nframes, const ScrollDynMaskRule *
     ScrollBatch::Mask &m = b->mk;
     hipStream_t hs = hip_stream ? (hipStream_t)hip_stream : b->own;
     const bool timed = b->timing != 0;
-    m.timed = 0;
-    if (timed && !m.ev[0])
-        for (hipEvent_t &e : m.ev) HIPCHK(hipEventCreate(&e));
-    if (timed) HIPCHK(hipEventRecord(m.ev[0], hs));
+    if ((rc = pass_begin(b, &m.run, 4, hs))) return rc;
 
     /* the compose's state pass, dry, and k_dyn_rows after it, as the QP probe
-     * runs them (probe_run): into the mask's own NalDesc / DynFrame /
-     * PlanPending / rows / heads / ctr, nothing committed.  Moving rects: the
-     * frames' own origins, and no dynamic NAL where there is no rect */
+     * runs them (probe_run): into the mask's own DryPlan and PredRows, nothing
+     * committed.  Moving rects: the frames' own origins, and no dynamic NAL
+     * where there is no rect */
     DynGeom G = b->geo;
     G.debug = b->debug;
-    G.gen_cap = (uint32_t)((size_t)b->max_streams * ld_fr);
     if ((rc = dyn_pos_table(b, hs, &G.dpos))) return rc;
-    const int plan = b->mode == SCROLL_MODE_EXPERIMENT ? SCROLL_PLAN_EXPERIMENT : SCROLL_PLAN_COMPOSER;
-    scroll_launch_plan(hs, S, b->d_st, b->d_off, b->max_frames, m.nal, b->ld_nal, nframes, plan,
-                       b->debug | PLAN_STATE | PLAN_DYN, m.pend, m.dfr, ld_fr, nullptr, 0u, 0u, m.ctr, G.dpos);
-    HIPCHK(hipGetLastError());
+    if ((rc = dry_plan_launch(b, hs, nframes, m.plan, 0, m.pr.ctr, G.dpos))) return rc;
     /* (no per-frame QP table: the prediction does not depend on the QP) */
-    if (dyn_launch_rows(hs, nframes, S, b->d_st, m.nal, b->ld_nal, m.pend, m.dfr, ld_fr, &G, m.rows, m.ctr, m.heads,
-                        nullptr)) {
-        set_err("k_dyn_rows launch: %s", hipGetErrorString(hipGetLastError()));
-        return SCROLL_ERR_HIP;
-    }
+    if ((rc = pred_rows_launch(b, hs, nframes, m.plan, m.pr, &G))) return rc;
     job.st = b->d_st;
-    job.nal = m.nal;
-    job.pend = m.pend;
-    job.dfr = m.dfr;
-    job.rows = m.rows;
-    job.ctr = m.ctr;
+    job.nal = m.plan.nal;
+    job.pend = m.plan.pend;
+    job.dfr = m.plan.dfr;
+    job.rows = m.pr.rows;
+    job.ctr = m.pr.ctr;
     job.src = b->d_src;
     job.refs = b->d_refs;
     job.map = m.map;
@@ -169,24 +124,17 @@ int scroll_batch_dyn_mask(ScrollBatch *b, int nframes, const ScrollDynMaskRule *
     job.ld_nal = b->ld_nal;
     job.ld_fr = ld_fr;
     job.rule = *rule;
-    if (mask_launch(hs, &job, timed ? m.ev[1] : nullptr, timed ? m.ev[2] : nullptr)) {
+    if (mask_launch(hs, &job, timed ? m.run.ev[1] : nullptr, timed ? m.run.ev[2] : nullptr)) {
         set_err("k_dyn_mask launch: %s", hipGetErrorString(hipGetLastError()));
         return SCROLL_ERR_HIP;
     }
-    if (timed) {
-        HIPCHK(hipEventRecord(m.ev[3], hs));
-        m.timed = 1;
-    }
-    HIPCHK(hipEventRecord(m.fin, hs));
-    m.nframes = nframes;
-    m.nstreams = S;
-    return SCROLL_OK;
+    return pass_end(b, &m.run, hs, nframes, S);
 }
 
 int scroll_batch_dyn_mask_result(ScrollBatch *b, int s, int f, ScrollDynMask *out)
 {
-    if (!out) return SCROLL_ERR_ARG;
-    int rc = mask_frame_arg(b, s, f, "scroll_batch_dyn_mask_result");
+    if (!b || !out) return SCROLL_ERR_ARG;
+    int rc = pass_frame_arg(b, &b->mk.run, s, f, "scroll_batch_dyn_mask_result", "mask", "scroll_batch_dyn_mask");
     if (rc) return rc;
     HIPCHK(hipMemcpy(out, b->mk.res + (size_t)s * b->max_frames + f, sizeof(*out), hipMemcpyDeviceToHost));
     return SCROLL_OK;
@@ -201,8 +149,8 @@ const ScrollDynMask *scroll_batch_dyn_mask_device(ScrollBatch *b, size_t *stream
 
 int scroll_batch_dyn_mask_map(ScrollBatch *b, int s, int f, uint32_t *dst)
 {
-    if (!dst) return SCROLL_ERR_ARG;
-    int rc = mask_frame_arg(b, s, f, "scroll_batch_dyn_mask_map");
+    if (!b || !dst) return SCROLL_ERR_ARG;
+    int rc = pass_frame_arg(b, &b->mk.run, s, f, "scroll_batch_dyn_mask_map", "mask", "scroll_batch_dyn_mask");
     if (rc) return rc;
     const size_t n = mask_frame_words(b);
     HIPCHK(hipMemcpy(dst, b->mk.map + ((size_t)s * b->max_frames + f) * n, n * sizeof(uint32_t),
@@ -219,23 +167,8 @@ const uint32_t *scroll_batch_dyn_mask_map_device(ScrollBatch *b, size_t *stream_
     return b->mk.map;
 }
 
-static float mask_span_ms(ScrollBatch *b, int from, int to)
-{
-    if (!b || !b->mk.res || !b->mk.timed) return -1.0f;
-    if (hipSetDevice(b->device) != hipSuccess || hipEventSynchronize(b->mk.ev[3]) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0f;
-    }
-    float ms = -1.0f;
-    if (hipEventElapsedTime(&ms, b->mk.ev[from], b->mk.ev[to]) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0f;
-    }
-    return ms;
-}
+float scroll_batch_dyn_mask_ms(ScrollBatch *b) { return b ? pass_span_ms(b, &b->mk.run, 0, 3) : -1.0f; }
 
-float scroll_batch_dyn_mask_ms(ScrollBatch *b) { return mask_span_ms(b, 0, 3); }
-
-float scroll_batch_dyn_mask_kernel_ms(ScrollBatch *b) { return mask_span_ms(b, 1, 2); }
+float scroll_batch_dyn_mask_kernel_ms(ScrollBatch *b) { return b ? pass_span_ms(b, &b->mk.run, 1, 2) : -1.0f; }
 
 }  // extern "C"

@@ -25,10 +25,7 @@ namespace batch {
 void rate_release(ScrollBatch *b)
 {
     ScrollBatch::Rate &r = b->rt;
-    if (r.fin) {
-        (void)hipEventSynchronize(r.fin);
-        (void)hipEventDestroy(r.fin);
-    }
+    pass_release(&r.run);
     (void)hipFree(r.level);
     (void)hipFree(r.fb);
     (void)hipFree(r.out);
@@ -67,7 +64,7 @@ static int table_refresh(ScrollBatch *b)
     if (rc) return rc;
     if (!b->dx.qpf || !b->qpf_dev) return SCROLL_OK;
     HIPCHK(hipSetDevice(b->device));
-    if (b->rt.fin) HIPCHK(hipEventSynchronize(b->rt.fin));
+    if (b->rt.run.fin) HIPCHK(hipEventSynchronize(b->rt.run.fin));
     HIPCHK(hipMemcpy(b->h_qpf.data(), b->dx.qpf, table_bytes(b), hipMemcpyDeviceToHost));
     /* (a pointer handed out stays with the caller: its kernels may write again) */
     return SCROLL_OK;
@@ -84,7 +81,7 @@ static int rate_alloc(ScrollBatch *b, const char *who)
     if (e == hipSuccess) e = hipMemset(r.level, 0, S * sizeof(long long));
     if (e == hipSuccess) e = hipMalloc(&r.fb, S * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&r.out, table_bytes(b) * sizeof(PickOut));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&r.fin, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&r.run.fin, hipEventDisableTiming);
     if (e != hipSuccess) {
         rate_release(b);
         return hip_fail(who, e, true);
@@ -157,7 +154,7 @@ int scroll_batch_clear_dyn_qp_frames(ScrollBatch *b)
     int rc = batch_host_sync(b);
     if (rc) return rc;
     HIPCHK(hipSetDevice(b->device));
-    if (b->rt.fin) HIPCHK(hipEventSynchronize(b->rt.fin));
+    if (b->rt.run.fin) HIPCHK(hipEventSynchronize(b->rt.run.fin));
     HIPCHK(hipMemset(b->dx.qpf, 0xFF, table_bytes(b)));
     HIPCHK(hipDeviceSynchronize());
     std::fill(b->h_qpf.begin(), b->h_qpf.end(), (uint8_t)0xFFu);
@@ -200,7 +197,7 @@ int scroll_batch_dyn_pick(ScrollBatch *b, int nframes, const ScrollDynRate *rate
         return SCROLL_ERR_ARG;
     }
     ScrollBatch::Probe &p = b->pb;
-    if (!p.res || p.nframes < 0 || p.hinted || nframes > p.nframes || p.nstreams != b->nstreams) {
+    if (p.run.nframes < 0 || p.hinted || nframes > p.run.nframes || p.run.nstreams != b->nstreams) {
         set_err("%s: needs a scroll_batch_dyn_probe (the plain one) of at least %d frames of the batch's streams "
                 "before it", who, nframes);
         return SCROLL_ERR_CONFIG;
@@ -225,14 +222,12 @@ int scroll_batch_dyn_pick(ScrollBatch *b, int nframes, const ScrollDynRate *rate
     const int S = b->nstreams;
     if (frame_bits_per_stream && S > 0)
         HIPCHK(hipMemcpyAsync(r.fb, frame_bits_per_stream, (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, hs));
-    if (pick_launch(hs, nframes, S, b->d_st, p.dfr, b->max_frames, p.res, p.done, b->geo.h, p.qps, p.nq, rate,
+    if (pick_launch(hs, nframes, S, b->d_st, p.plan.dfr, b->max_frames, p.res, p.done, b->geo.h, p.qps, p.nq, rate,
                     frame_bits_per_stream ? r.fb : nullptr, r.level, b->dx.qpf, r.out)) {
         set_err("k_dyn_pick launch: %s", hipGetErrorString(hipGetLastError()));
         return SCROLL_ERR_HIP;
     }
-    HIPCHK(hipEventRecord(r.fin, hs));
-    r.nframes = nframes;
-    r.nstreams = S;
+    if ((rc = pass_end(b, &r.run, hs, nframes, S))) return rc;
     b->qpf_dev = 1;
     return SCROLL_OK;
 }
@@ -240,20 +235,10 @@ int scroll_batch_dyn_pick(ScrollBatch *b, int nframes, const ScrollDynRate *rate
 int scroll_batch_dyn_pick_result(ScrollBatch *b, int s, int f, int *k, int *qp)
 {
     if (!b) return SCROLL_ERR_ARG;
-    ScrollBatch::Rate &r = b->rt;
-    if (!r.out || r.nframes < 0) {
-        set_err("scroll_batch_dyn_pick_result: no pick to read (scroll_batch_dyn_pick; scroll_batch_set_dyn_rect "
-                "drops it)");
-        return SCROLL_ERR_CONFIG;
-    }
-    if (s < 0 || s >= r.nstreams || f < 0 || f >= r.nframes) {
-        set_err("scroll_batch_dyn_pick_result: stream %d / frame %d outside the last pick", s, f);
-        return SCROLL_ERR_ARG;
-    }
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(hipEventSynchronize(r.fin));
+    const int rc = pass_frame_arg(b, &b->rt.run, s, f, "scroll_batch_dyn_pick_result", "pick", "scroll_batch_dyn_pick");
+    if (rc) return rc;
     PickOut o;
-    HIPCHK(hipMemcpy(&o, r.out + (size_t)s * b->max_frames + f, sizeof(o), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&o, b->rt.out + (size_t)s * b->max_frames + f, sizeof(o), hipMemcpyDeviceToHost));
     if (k) *k = -1;
     if (qp) *qp = -1;
     if (o.status == PICK_SHORT) {
@@ -279,7 +264,7 @@ int scroll_batch_dyn_rate_level(ScrollBatch *b, int s, int64_t *level, int set)
     }
     int rc = rate_alloc(b, who);
     if (rc) return rc;
-    HIPCHK(hipEventSynchronize(b->rt.fin));     /* (never recorded: complete) */
+    HIPCHK(hipEventSynchronize(b->rt.run.fin)); /* (never recorded: complete) */
     long long v = (long long)*level;
     if (set) {
         HIPCHK(hipMemcpy(b->rt.level + s, &v, sizeof(v), hipMemcpyHostToDevice));

@@ -30,12 +30,7 @@ void surface_release(ScrollBatch *b, bool all)
     (void)hipFree(sf.pos);
     sf.pos = nullptr;
     sf.h_pos.clear();
-    if (!all) return;
-    for (hipEvent_t &e : sf.ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    sf.timed = 0;
+    if (all) pass_release(&sf.run);
 }
 
 /* what every surface call asks of the surfaces: w pixels of every row lie inside the pitch */
@@ -70,23 +65,14 @@ int surf_args(const char *who, const ScrollSurfaces *surf, uint64_t w, bool stre
 /* the launches of one conversion, between the timing events when timing is on */
 static int surf_run(ScrollBatch *b, hipStream_t hs, const CscJob &job, const char *who)
 {
-    ScrollBatch::Surf &sf = b->sf;
-    const bool timed = b->timing != 0;
-    sf.timed = 0;
-    if (timed && !sf.ev[0]) {
-        HIPCHK(hipEventCreate(&sf.ev[0]));
-        HIPCHK(hipEventCreate(&sf.ev[1]));
-    }
-    if (timed) HIPCHK(hipEventRecord(sf.ev[0], hs));
+    const int rc = pass_begin(b, &b->sf.run, 2, hs);
+    if (rc) return rc;
     if (csc_launch(hs, &job)) {
         set_err("%s: k_csc launch: %s", who, hipGetErrorString(hipGetLastError()));
         return SCROLL_ERR_HIP;
     }
-    if (timed) {
-        HIPCHK(hipEventRecord(sf.ev[1], hs));
-        sf.timed = 1;
-    }
-    return SCROLL_OK;
+    /* (the timing only: sf.fin is not the end of a run) */
+    return pass_stop(b, &b->sf.run, hs);
 }
 
 extern "C" {
@@ -227,13 +213,6 @@ int scroll_batch_set_dyn_refs_device(ScrollBatch *b, int s, const uint8_t *d_ref
     return dyn_set_refs(b, s, d_ref_a, d_ref_b, hipMemcpyDeviceToDevice);
 }
 
-float scroll_batch_surface_ms(ScrollBatch *b)
-{
-    if (!b || !b->sf.timed) return -1.0f;
-    if (hipSetDevice(b->device) != hipSuccess || hipEventSynchronize(b->sf.ev[1]) != hipSuccess) return -1.0f;
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, b->sf.ev[0], b->sf.ev[1]) != hipSuccess) return -1.0f;
-    return ms;
-}
+float scroll_batch_surface_ms(ScrollBatch *b) { return b ? pass_span_ms(b, &b->sf.run, 0, 1) : -1.0f; }
 
 }  // extern "C"

@@ -863,6 +863,33 @@ class Batch:
         launches (-1 without)"""
         return lib.scroll_batch_surface_ms(self.h)
 
+    # ---- what the side passes' accessors share ----
+    def _records(self, fn, what, rec, dtype, nframes):
+        """fn's record of every frame: a structured array [S][nframes], a ctypes array field as a tuple"""
+        import numpy as np
+        out = np.zeros((self.num_streams, nframes), dtype=dtype)
+        for s in range(out.shape[0]):
+            for f in range(nframes):
+                self._chk(fn(self.h, s, f, ctypes.byref(rec)), what)
+                vals = (getattr(rec, n) for n in out.dtype.names)
+                out[s, f] = tuple(tuple(v) if isinstance(v, ctypes.Array) else v for v in vals)
+        return out
+
+    def _maps(self, fn, what, nframes, shape):
+        """fn's uint32 map of every frame: [S][nframes] + shape"""
+        import numpy as np
+        out = np.zeros((self.num_streams, nframes) + shape, dtype=np.uint32)
+        for s in range(out.shape[0]):
+            for f in range(nframes):
+                self._chk(fn(self.h, s, f, out[s, f].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), what)
+        return out
+
+    def _device(self, fn, nstrides):
+        """(device pointer, stride, ...) as fn hands them out"""
+        strides = [ctypes.c_size_t() for _ in range(nstrides)]
+        p = fn(self.h, *[ctypes.byref(v) for v in strides])
+        return (p,) + tuple(v.value for v in strides)
+
     # ---- the rect located from the surfaces ----
     def dyn_locate(self, ptr, nframes, pitch, frame_stride, stream_stride=0, fmt=SCROLL_SURF_RGBA,
                    matrix=SCROLL_SURF_BT601, full_range=False, mb_sse=0, margin=0, apply=True, stream=None,
@@ -887,39 +914,21 @@ class Batch:
         """the last dyn_locate's records: a numpy structured array [S][nframes]
         with ScrollDynDamage's fields (x0 = -1: no rect; status
         SCROLL_DYN_LOC_*).  Synchronises"""
-        import numpy as np
-        out = np.zeros((self.num_streams, nframes), dtype=_damage_dtype())
-        r = ScrollDynDamage()
-        for s in range(out.shape[0]):
-            for f in range(nframes):
-                self._chk(lib.scroll_batch_dyn_locate_result(self.h, s, f, ctypes.byref(r)), "dyn_locate_result")
-                out[s, f] = tuple(getattr(r, n) for n in out.dtype.names)
-        return out
+        return self._records(lib.scroll_batch_dyn_locate_result, "dyn_locate_result", ScrollDynDamage(),
+                             _damage_dtype(), nframes)
 
     def dyn_damage_map(self, nframes):
         """the last dyn_locate's map: uint32 [S][nframes][mbh][mbw].  Synchronises"""
-        import numpy as np
         c = self.config(0)
-        mbw, mbh = c.width // 16, c.height // 16
-        out = np.zeros((self.num_streams, nframes, mbh, mbw), dtype=np.uint32)
-        for s in range(out.shape[0]):
-            for f in range(nframes):
-                self._chk(lib.scroll_batch_dyn_damage_map(self.h, s, f,
-                                                          out[s, f].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
-                          "dyn_damage_map")
-        return out
+        return self._maps(lib.scroll_batch_dyn_damage_map, "dyn_damage_map", nframes, (c.height // 16, c.width // 16))
 
     def dyn_locate_device(self):
         """(device pointer, stream stride in bytes) of the records, ScrollDynDamage [stream][frame]"""
-        ls = ctypes.c_size_t()
-        p = lib.scroll_batch_dyn_locate_device(self.h, ctypes.byref(ls))
-        return p, ls.value
+        return self._device(lib.scroll_batch_dyn_locate_device, 1)
 
     def dyn_damage_map_device(self):
         """(device pointer, stream stride, frame stride in bytes) of the map, uint32 [stream][frame][mbh][mbw]"""
-        ls, lf = ctypes.c_size_t(), ctypes.c_size_t()
-        p = lib.scroll_batch_dyn_damage_map_device(self.h, ctypes.byref(ls), ctypes.byref(lf))
-        return p, ls.value, lf.value
+        return self._device(lib.scroll_batch_dyn_damage_map_device, 2)
 
     def dyn_locate_ms(self, kernel=False):
         """with enable_timing: HIP-event ms of the last dyn_locate's launches
@@ -943,38 +952,21 @@ class Batch:
         """the last dyn_mask's records: a numpy structured array [S][nframes]
         with ScrollDynMask's fields (status SCROLL_DYN_MASK_*; sse_drop: Y, Cb,
         Cr).  Synchronises"""
-        import numpy as np
-        out = np.zeros((self.num_streams, nframes), dtype=_mask_dtype())
-        r = ScrollDynMask()
-        for s in range(out.shape[0]):
-            for f in range(nframes):
-                self._chk(lib.scroll_batch_dyn_mask_result(self.h, s, f, ctypes.byref(r)), "dyn_mask_result")
-                out[s, f] = (r.status, r.n_changed, r.n_kept, r.reserved, tuple(r.sse_drop))
-        return out
+        return self._records(lib.scroll_batch_dyn_mask_result, "dyn_mask_result", ScrollDynMask(), _mask_dtype(),
+                             nframes)
 
     def dyn_mask_map(self, nframes, w, h):
         """the last dyn_mask's map for the w x h rect: uint32 [S][nframes][h][w][2],
         { Dy, Dc | SCROLL_DYN_MASK_KEPT } per MB.  Synchronises"""
-        import numpy as np
-        out = np.zeros((self.num_streams, nframes, h, w, 2), dtype=np.uint32)
-        for s in range(out.shape[0]):
-            for f in range(nframes):
-                self._chk(lib.scroll_batch_dyn_mask_map(self.h, s, f,
-                                                        out[s, f].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
-                          "dyn_mask_map")
-        return out
+        return self._maps(lib.scroll_batch_dyn_mask_map, "dyn_mask_map", nframes, (h, w, 2))
 
     def dyn_mask_device(self):
         """(device pointer, stream stride in bytes) of the records, ScrollDynMask [stream][frame]"""
-        ls = ctypes.c_size_t()
-        p = lib.scroll_batch_dyn_mask_device(self.h, ctypes.byref(ls))
-        return p, ls.value
+        return self._device(lib.scroll_batch_dyn_mask_device, 1)
 
     def dyn_mask_map_device(self):
         """(device pointer, stream stride, frame stride in bytes) of the map, uint32 [stream][frame][h][w][2]"""
-        ls, lf = ctypes.c_size_t(), ctypes.c_size_t()
-        p = lib.scroll_batch_dyn_mask_map_device(self.h, ctypes.byref(ls), ctypes.byref(lf))
-        return p, ls.value, lf.value
+        return self._device(lib.scroll_batch_dyn_mask_map_device, 2)
 
     def dyn_mask_ms(self, kernel=False):
         """with enable_timing: HIP-event ms of the last dyn_mask's launches
@@ -1004,14 +996,8 @@ class Batch:
         """the last detect_offsets' records: a numpy structured array
         [S][nframes] with ScrollOffsetFound's fields (status SCROLL_DET_*).
         Synchronises"""
-        import numpy as np
-        out = np.zeros((self.num_streams, nframes), dtype=_detect_dtype())
-        r = ScrollOffsetFound()
-        for s in range(out.shape[0]):
-            for f in range(nframes):
-                self._chk(lib.scroll_batch_detect_result(self.h, s, f, ctypes.byref(r)), "detect_result")
-                out[s, f] = tuple(getattr(r, n) for n in out.dtype.names)
-        return out
+        return self._records(lib.scroll_batch_detect_result, "detect_result", ScrollOffsetFound(), _detect_dtype(),
+                             nframes)
 
     def detect_scores(self, s, f):
         """the last detect_offsets' scores of one frame: uint32 [ph + 1],
@@ -1024,15 +1010,11 @@ class Batch:
 
     def detect_device(self):
         """(device pointer, stream stride in bytes) of the records, ScrollOffsetFound [stream][frame]"""
-        ls = ctypes.c_size_t()
-        p = lib.scroll_batch_detect_device(self.h, ctypes.byref(ls))
-        return p, ls.value
+        return self._device(lib.scroll_batch_detect_device, 1)
 
     def detect_scores_device(self):
         """(device pointer, stream stride, frame stride in bytes) of the scores, uint32 [stream][frame][ph + 1]"""
-        ls, lf = ctypes.c_size_t(), ctypes.c_size_t()
-        p = lib.scroll_batch_detect_scores_device(self.h, ctypes.byref(ls), ctypes.byref(lf))
-        return p, ls.value, lf.value
+        return self._device(lib.scroll_batch_detect_scores_device, 2)
 
     def detect_ms(self, kernel=False, score=False):
         """with enable_timing: HIP-event ms of the last detect_offsets'
@@ -1141,9 +1123,7 @@ class Batch:
     def dyn_probe_device(self):
         """(device pointer, stream stride, frame stride) of the last probe's
         results, ScrollDynProbe [stream][frame][SCROLL_DYN_PROBE_MAX_QPS]"""
-        ls, lf = ctypes.c_size_t(), ctypes.c_size_t()
-        p = lib.scroll_batch_dyn_probe_device(self.h, ctypes.byref(ls), ctypes.byref(lf))
-        return p, ls.value, lf.value
+        return self._device(lib.scroll_batch_dyn_probe_device, 2)
 
     def dyn_probe_ms(self):
         """with enable_timing: HIP-event ms of the last probe's launches (-1
@@ -1189,9 +1169,7 @@ class Batch:
     def dyn_qp_frames_device(self):
         """(device pointer, stream stride) of the per-frame QP table, one byte
         per frame, 0xFF: the stream's QP"""
-        ls = ctypes.c_size_t()
-        p = lib.scroll_batch_dyn_qp_frames_device(self.h, ctypes.byref(ls))
-        return p, ls.value
+        return self._device(lib.scroll_batch_dyn_qp_frames_device, 1)
 
     def dyn_pick(self, nframes, frame_bits, bucket_bits=None, per_stream=None, stream=None):
         """the per-frame QPs of the next compose(nframes), picked on the device
